@@ -19,26 +19,32 @@ Scaling modes (one process per GPU under torchrun, RCCL = backend "nccl"):
   --pairs P: P pairs per GPU ("scaling": "weak").
 Every step ends with one all_gather_into_tensor of the per-cell records.
 
-The line also carries two labelled blocks beside the headline:
+A plain run sets up, warms up, times the K steps and prints the line: the
+headline, "roofline" (the enhance kernel's HIP-event time in the timed steps
+against VALU lane-op throughput, the resource it spends: each instruction
+priced at the SIMD cycles it takes, from the committed counters; the measured
+HBM GB/s and SURVEY §8(d)'s algorithmic byte figure beside it), "clock" and
+"ranks".  --dump-outputs DIR then saves what the last timed step returned
+(dump_outputs).
+
+With --full the line also carries, each from runs of its own after the timed
+steps:
   full_grid     the same step over the whole HEAD grid, both n_fft halves
                 (9,744 cells per pair), with each half's kernel time;
   sweep         the reference's whole job through search.run_grid: alignment,
                 SNR and STOI of every cell, the gather and both sequential
                 selections, wall seconds and cells/s;
-and "roofline", the enhance kernel against VALU lane-op throughput (the
-resource it spends: each instruction priced at the SIMD cycles it takes), with
-the measured HBM GB/s and SURVEY §8(d)'s algorithmic byte figure beside it.
-
-At N = 1 the line also carries
   parity        the timed step's per-cell SNR table of pair 0 against the
                 oracle on every cell the CPU baseline computed, and the
                 waveforms of 64 cells stratified over algorithm x hop x noise
                 method against the oracle (north-star: rel-L2 and rel-max
                 <= 1e-5); the run fails above tolerance;
-  cpu_baseline  the oracle on this host's cores (see cpu_baseline()).
+  cpu_baseline  (at N = 1) the oracle on this host's cores (see cpu_run()).
 
     python bench.py [--gpus N --steps K --warmup W --pairs-total 100 | --pairs P]
-                    [--full-grid-steps F] [--no-sweep]
+                    [--dump-outputs DIR]
+                    [--full [--full-grid-steps F] [--no-sweep] [--no-parity]
+                            [--no-cpu-baseline]]
 """
 
 import argparse
@@ -572,6 +578,30 @@ def gather_rank_stats(stats, dist_ctx):
                        "share of one step")}
 
 
+DUMP_LIMIT = 60 << 20          # bytes of array data per --dump-outputs directory
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step returned, one <name>.npy each,
+    f64 as computed (anything else as f32):
+      records  [cells, 2] (sse, finite) of every cell of the job by global cell
+               id, from the records the step gathered to the host;
+      snr_db   the lag-0 SNR of rank 0's cells from those sums, in the order of
+               their global cell ids (at one rank: every cell).
+    The inputs are synth.make_pair's seeded pairs, so the same arguments give
+    the same job from run to run.  A job whose arrays exceed DUMP_LIMIT keeps
+    of each array a fixed (seed 0) sorted sample of rows in proportion."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, len(a) * DUMP_LIMIT // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -605,9 +635,18 @@ def main():
                          "(sse, finite) by global cell id to this .npy (multi-rank tests)")
     ap.add_argument("--no-sweep", action="store_true",
                     help="skip the sweep block (search.run_grid with alignment and STOI)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the full_grid, sweep, parity "
+                         "and cpu_baseline blocks (--full-grid-steps 0, --no-sweep, --no-parity "
+                         "and --no-cpu-baseline drop single blocks of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step returned as DIR/<name>.npy "
+                         "(records, snr_db: see dump_outputs)")
     args = ap.parse_args()
     if args.pipeline < 1:
         ap.error("--pipeline must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
     import torch.distributed as dist
@@ -650,12 +689,15 @@ def main():
     assert fin.all(), "non-finite enhanced output"
     snr_local = snr_db(sse, clean_pow[[s for (s, _, _) in local_specs]])
     assert np.isfinite(snr_local).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"records": table, "snr_db": snr_local})
     del job
 
+    # everything below the headline runs only with --full
     # ---- full_grid: both n_fft halves of the HEAD grid per step (9,744 cells per pair)
     full = None
     fsteps = min(args.steps, 5) if args.full_grid_steps is None else args.full_grid_steps
-    if fsteps > 0:
+    if args.full and fsteps > 0:
         f_ids, f_specs, f_gids, f_units, _ = rank_job(args, world, rank, None)
         f_pairs = [make_pair(i, args.seconds) for i in f_ids]
         f_clean = torch.as_tensor(np.stack([c for c, _ in f_pairs])).cuda()
@@ -680,7 +722,7 @@ def main():
     # :156-226) through search.run_grid: every cell aligned, SNR and STOI scored,
     # records gathered, both sequential selections
     sweep = None
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         torch.cuda.empty_cache()  # the timed jobs' plans are gone: their memory goes back
         sweep = sweep_block(args, world, total_pairs, weak)
 
@@ -688,10 +730,11 @@ def main():
     # cells' waveforms and the timed step's SNRs against the oracle; at N = 1
     # the CPU baseline runs in the same pool (rank 0 only)
     base, par = None, None
-    want_base = rank == 0 and world == 1 and not args.no_cpu_baseline
-    if not args.no_parity or want_base:
+    want_par = args.full and not args.no_parity
+    want_base = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if want_par or want_base:
         slot, held = rank_pair_cells(local_specs, args.nfft)
-        y_cells = [] if args.no_parity else pick_parity_cells(args.seconds, args.nfft, held)
+        y_cells = pick_parity_cells(args.seconds, args.nfft, held) if want_par else []
         base, cpu_snr, cpu_y = cpu_run(args.cpu_budget, args.seconds, args.nfft, y_cells,
                                        timed=want_base, pair=pair_ids[slot])
         if y_cells:
@@ -699,7 +742,7 @@ def main():
             par = parity_block(eng, noisy[slot:slot + 1], clean[slot:slot + 1], clean_pow[slot],
                                args.nfft, dev_snr, cpu_snr, cpu_y)
             par["pair"] = int(pair_ids[slot])
-    par_all = gather_parity(par, dist_ctx) if not args.no_parity else None
+    par_all = gather_parity(par, dist_ctx) if want_par else None
 
     if rank != 0:
         if use_dist:
@@ -714,6 +757,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": dt / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak" if weak else "strong",

@@ -187,3 +187,24 @@ def test_kernel_digest_ignores_comments_only():
     assert bench.code_text(t) == 'int a = 1; const char* s = "// kept /* kept */"; char q = \'/\';'
     assert bench.code_text("int a = 1;") != bench.code_text("int a = 2;")
     assert len(bench.kernel_src_sha()) == 16
+
+
+def test_dump_outputs_keeps_values_and_caps_the_size(tmp_path, monkeypatch):
+    """--dump-outputs: f64 stays f64, other types become f32, values unchanged;
+    above DUMP_LIMIT every array keeps the same seeded sorted sample of its
+    rows from call to call and the directory's data stays within the limit."""
+    rec = np.arange(2000, dtype=np.float64).reshape(1000, 2)
+    snr = np.arange(1000, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"records": rec, "snr_db": snr})
+    a = np.load(tmp_path / "a" / "records.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, rec)
+    b = np.load(tmp_path / "a" / "snr_db.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, snr)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 5000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"records": rec, "snr_db": snr})
+    r1, r2 = np.load(tmp_path / "b" / "records.npy"), np.load(tmp_path / "c" / "records.npy")
+    s1 = np.load(tmp_path / "b" / "snr_db.npy")
+    assert np.array_equal(r1, r2) and 0 < len(r1) < 1000
+    assert r1.nbytes + s1.nbytes <= 5000
+    assert np.all(np.diff(r1[:, 0]) > 0) and np.all(r1[:, 1] == r1[:, 0] + 1)  # whole rows, in order

@@ -40,7 +40,7 @@ def test_bench_two_ranks_weak_scaling(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--pairs", "1", "--seconds", "2", "--no-cpu-baseline"]
+           "--pairs", "1", "--seconds", "2", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -96,7 +96,7 @@ def test_bench_two_ranks_strong_scaling(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--pairs-total", "3", "--seconds", "2", "--no-cpu-baseline"]
+           "--pairs-total", "3", "--seconds", "2", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -116,11 +116,43 @@ def test_bench_rccl_world1(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
-           "--pairs-total", "2", "--seconds", "2", "--no-cpu-baseline", "--no-parity"]
+           "--pairs-total", "2", "--seconds", "2", "--full", "--no-cpu-baseline", "--no-parity"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and "RCCL" in d["config"]["parallelism"]
+
+
+def test_bench_plain_run_headline_only_and_dumped_outputs(gpu, tmp_path):
+    """A plain run times --steps steps and prints the headline without the
+    --full blocks; --dump-outputs saves the last step's records and SNRs, and
+    two runs with the same arguments (started side by side) save the same
+    arrays bit for bit."""
+    outs = [tmp_path / "a", tmp_path / "b"]
+    procs = [subprocess.Popen([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1",
+                               "--steps", "3", "--warmup", "1", "--pairs-total", "1",
+                               "--seconds", "1", "--dump-outputs", str(o)], cwd=REPO,
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for o in outs]
+    res = [p.communicate(timeout=240) for p in procs]
+    for p, (_, err) in zip(procs, res):
+        assert p.returncode == 0, err[-2000:]
+    lines = [l for l in res[0][0].splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res[0][0]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["value"] == pytest.approx(d["config"]["units_per_step"] / (d["ms_per_step"] / 1e3),
+                                       rel=1e-6)
+    assert d["higher_is_better"] is True and d["unit"] == "frame-gain evals/s" and d["dtype"]
+    assert not {"full_grid", "sweep", "parity", "cpu_baseline"} & set(d)
+    rec, snr = np.load(outs[0] / "records.npy"), np.load(outs[0] / "snr_db.npy")
+    assert rec.dtype == snr.dtype == np.float64
+    assert rec.shape == (4872, 2) and snr.shape == (4872,)
+    assert np.all(rec[:, 1] == 1) and np.all(rec[:, 0] > 0) and np.isfinite(snr).all()
+    # one pair: SNR differences between cells are the sse ratios in dB
+    assert np.allclose(snr - snr[0], -10 * np.log10(rec[:, 0] / rec[0, 0]), atol=1e-6)
+    assert np.array_equal(rec, np.load(outs[1] / "records.npy"))
+    assert np.array_equal(snr, np.load(outs[1] / "snr_db.npy"))
 
 
 def _rccl_rank(rank, world, port, outdir):
@@ -167,8 +199,8 @@ def test_bench_eight_ranks_strong_scaling_rehearsal(gpu, tmp_path):
     first hardware run: per-rank kernel / analysis / wall time, units, cells
     and pairs with their max / mean spread, and a parity check on every rank
     (its most-held pair's stratified cells against the oracle)."""
-    common = ["--steps", "1", "--warmup", "1", "--pairs-total", "100", "--full-grid-steps", "0",
-              "--no-sweep", "--no-cpu-baseline"]
+    common = ["--steps", "1", "--warmup", "1", "--pairs-total", "100", "--full",
+              "--full-grid-steps", "0", "--no-sweep", "--no-cpu-baseline"]
     # 8 ranks share this box's CPU share: 2 oracle processes each
     env = dict(os.environ, CSE_DIST_BACKEND="gloo", CSE_CPU_BASELINE_PROCS="2")
     t8, t1 = tmp_path / "t8.npy", tmp_path / "t1.npy"

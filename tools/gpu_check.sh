@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 TESTS=${TESTS:-tests}
-BENCH_ARGS=${BENCH_ARGS:---steps 20 --warmup 5}
+BENCH_ARGS=${BENCH_ARGS:---steps 20 --warmup 5 --full}
 stop() { case $1 in 0|1) return 1 ;; *) return 0 ;; esac; }
 timeout -k 10 ${TEST_LIMIT:-900} python -u -m pytest $TESTS -m gpu -x -v -s --timeout 420 \
     --timeout-method thread > gpurun_out/tests.log 2>&1

@@ -24,7 +24,7 @@ def main(tag, units, rnd="r01"):
         "kernel": "cse::enhance_kernel<512, false>",
         "round": rnd,
         "command": ("rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (separate passes) -- "
-                    "python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline"),
+                    "python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline"),
         "units_per_launch": int(units),
         "fetch_size_kb_raw": fetch_kb, "write_size_kb_raw": write_kb,
         "correction": "gfx950: FETCH_SIZE x2 (half-counted streaming reads); KiB -> x1024",
