@@ -1,4 +1,5 @@
-"""ctypes binding of libcse.so (the C ABI declared in include/cse.h).
+"""ctypes binding of libcse.so (the C ABI declared in include/cse.h and
+include/cse_estoi.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -56,6 +57,8 @@ EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_stoi_workspace_bytes", "cse_stoi_scratch_bytes", "cse_stoi_prepare",
            "cse_stoi_cells", "cse_stoi_workspace_bytes_sr", "cse_stoi_scratch_bytes_sr",
            "cse_stoi_cells_sr")
+# include/cse_estoi.h (extended STOI), a header of its own: EXPORTS is what cse.h declares
+EXPORTS_ESTOI = ("cse_estoi_workspace_bytes", "cse_estoi_prepare", "cse_estoi_cells")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -139,6 +142,12 @@ def load(path=LIB_PATH):
     lib.cse_stoi_scratch_bytes_sr.argtypes = [i64, i64, i32]
     lib.cse_stoi_cells_sr.restype = i32
     lib.cse_stoi_cells_sr.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
+    lib.cse_estoi_workspace_bytes.restype = i64
+    lib.cse_estoi_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cse_estoi_prepare.restype = i32
+    lib.cse_estoi_prepare.argtypes = [P, i64, i64, i32, P, P]
+    lib.cse_estoi_cells.restype = i32
+    lib.cse_estoi_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

@@ -34,12 +34,18 @@
 //            energies -> envelope rows in a scratch buffer;
 //   phase B  tiles of 64 segments x 15 bands from LDS, one (segment, band)
 //            correlation per thread, fp64 accumulation.
+// Extended STOI (cse_estoi_*, defined in include/cse_estoi.h) shares all of
+// this but the correlations: estoi_cells_kernel is the same body with the
+// extended phase B (estoi_tile: rows, then columns of each segment mean-removed
+// and normalised), against column statistics cse_estoi_prepare adds to the
+// clean side (stoi_clean_col_kernel).
 // All arithmetic is fp64, like the reference: STOI normalises every band of
 // every 30-frame segment separately, so a band that holds only a noise floor
 // turns an fp32 FFT's roundoff (~1e-7 of the frame energy) into a visible
 // score error (measured: 1e-5 STOI on a synthetic pair).  The 16-kHz cell
 // outputs themselves are f32 (the enhance kernel's output type).
 #include "cse_common.hpp"
+#include "cse_estoi.h"
 
 #include <math.h>
 #include <numeric>
@@ -85,6 +91,7 @@ static_assert(SSTR >= 8 * (GRP + 15) + 8 && SSTR % 4 == 0, "staging slot stride"
 // at best, left the product in r04: tools/stoi_mf.md says how to rebuild it)
 constexpr int STAGE_F = SLOTS * SSTR;
 constexpr int NT = 256;                  // threads per workgroup
+constexpr int EHALF = 32;                // segments per half tile of the extended phase B
 constexpr double EPS = 2.220446049250313e-16; // np.finfo(float).eps
 __constant__ int BAND_EDGE[NBAND + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55,
                                          69, 87, 109, 138, 174, 219};
@@ -559,11 +566,18 @@ struct StoiLds {
         struct {
             double y[94 * 17];
             double x[94 * 17];
+            // extended phase B only: row mean and 1/(norm + eps) of y per
+            // (segment, band) of a half tile, in the room the union has
+            // beside the two envelope tiles (its size is t's)
+            double ym[stoi::EHALF * 17];
+            double yi[stoi::EHALF * 17];
         } b;
     } u;
     double red[stoi::NT / 64];
     int tab[2][stoi::BT];  // this block's table and the next one's (prefetch)
 };
+static_assert(sizeof(StoiLds::u) == sizeof(double) * stoi::FB * 16 * 17,
+              "the extended row statistics must not grow StoiLds");
 
 // e (16 kHz) sample n of a cell: the finalize_enhanced output — y shifted by
 // the alignment lag, length-matched (zero outside [0, len)), clipped
@@ -590,8 +604,11 @@ __device__ __forceinline__ void stoi_tables(StoiLds& L) {
 
 // PRE: the 10-kHz signal is given (fp64 x10: the clean side, and the cells at
 // input rates other than 16 kHz); otherwise the 16-kHz cell output is
-// resampled here.
-template <bool PRE>
+// resampled here.  EXT changes nothing in here: it gives the extended kernels
+// an instantiation (and lambdas) of their own.  With the 16-kHz instantiation
+// shared by two kernels, stoi_cells_kernel compiled to other code than it does
+// alone (7 of its 23 paired LDS stores split, 14 instructions more).
+template <bool PRE, bool EXT = false>
 __device__ __forceinline__ void stoi_phase_a(StoiLds& L, const float* __restrict__ y, int64_t len,
                                              int lag, bool clip, const double* __restrict__ x10,
                                              const double* __restrict__ coef,
@@ -875,6 +892,40 @@ __global__ void __launch_bounds__(256) stoi_clean_stat_kernel(const double* __re
     xstat[((int64_t)sig * Jmax + j) * 16 + b] = make_double4(sqrt(s2), mean, 1.0 / (sqrt(c2) + EPS), 0.0);
 }
 
+// Extended STOI (include/cse_estoi.h), clean side: per (segment j, frame t) the
+// mean over the 15 bands and 1/(norm + eps) of the row-normalised clean
+// segment's column, xr[b] = (x[j + t][b] - mean_b) inv_b with the row
+// statistics of stoi_clean_stat_kernel (xstat.y, xstat.z).  xcol [sig][Jmax][30].
+__global__ void __launch_bounds__(256) stoi_clean_col_kernel(const double* __restrict__ xtob,
+                                                              int64_t Mmax, int64_t Jmax,
+                                                              const int* __restrict__ meta,
+                                                              const double4* __restrict__ xstat,
+                                                              double2* __restrict__ xcol) {
+    using namespace stoi;
+    const int sig = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int J = meta[META * sig + 2];
+    const int j = (int)(i / NSEG), t = (int)(i % NSEG);
+    if (j >= J) return;
+    const double* x = xtob + ((int64_t)sig * Mmax + j + t) * 16;
+    const double4* st = xstat + ((int64_t)sig * Jmax + j) * 16;
+    double xr[NBAND];
+    double s = 0.0;
+#pragma unroll
+    for (int b = 0; b < NBAND; ++b) {
+        xr[b] = (x[b] - st[b].y) * st[b].z;
+        s += xr[b];
+    }
+    const double mean = s / NBAND;
+    double c2 = 0.0;
+#pragma unroll
+    for (int b = 0; b < NBAND; ++b) {
+        const double v = xr[b] - mean;
+        c2 = fma(v, v, c2);
+    }
+    xcol[((int64_t)sig * Jmax + j) * NSEG + t] = make_double2(mean, 1.0 / (sqrt(c2) + EPS));
+}
+
 // ---------------------------------------------------------------------------
 // per cell: phase A into env scratch, phase B correlations -> stoi[c]
 // ---------------------------------------------------------------------------
@@ -894,13 +945,94 @@ struct StoiArgs {
     double* out;
 };
 
+// Extended phase B (include/cse_estoi.h) of the tile of segments [j0, j0 + 64)
+// that the caller loaded into L.u.b, in halves of EHALF segments (the row
+// statistics of a half fit beside the tiles):
+//   (a) one thread per (segment, band) holds the band's 30 frames and writes
+//       the mean and 1/(norm + eps) of y's row;
+//   (c) one work item per (segment, frame) walks the 15 bands: row-normalised
+//       y and x (x's row statistics from xstat), y's column mean and norm here,
+//       x's from xcol (stoi_clean_col_kernel), sum over the bands of the
+//       products of the twice-normalised values.
+// Returns the thread's share of the sum over the tile.  Consecutive work
+// items are consecutive frames of one segment: a wave reads the statistics
+// of 3 or 4 segments (broadcast) and xcol contiguously.
+__device__ __forceinline__ double estoi_tile(StoiLds& L, int j0, int J,
+                                             const double4* __restrict__ xs,
+                                             const double2* __restrict__ xc) {
+    using namespace stoi;
+    const int tid = threadIdx.x;
+    const int nt = min(64, J - j0);
+    double acc = 0.0;
+    for (int h0 = 0; h0 < nt; h0 += EHALF) {
+        const int ns = min(EHALF, nt - h0);
+        if (h0) __syncthreads();  // the first half's readers of ym / yi are done
+        {
+            const int seg = tid & (EHALF - 1);
+            if (seg < ns) {
+#pragma unroll 1
+                for (int b = tid / EHALF; b < NBAND; b += NT / EHALF) {
+                    const double* yr = L.u.b.y + (h0 + seg) * 17 + b;
+                    double yv[NSEG];
+                    double s = 0.0;
+#pragma unroll
+                    for (int t = 0; t < NSEG; ++t) {
+                        yv[t] = yr[t * 17];
+                        s += yv[t];
+                    }
+                    const double my = s / NSEG;
+                    double c2 = 0.0;
+#pragma unroll
+                    for (int t = 0; t < NSEG; ++t) {
+                        const double d = yv[t] - my;
+                        c2 = fma(d, d, c2);
+                    }
+                    L.u.b.ym[seg * 17 + b] = my;
+                    L.u.b.yi[seg * 17 + b] = 1.0 / (sqrt(c2) + EPS);
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < ns * NSEG; i += NT) {
+            const int seg = i / NSEG, t = i - NSEG * seg;
+            const int64_t j = j0 + h0 + seg;
+            const double* yr = L.u.b.y + (h0 + seg + t) * 17;
+            const double* xr = L.u.b.x + (h0 + seg + t) * 17;
+            const double* ym = L.u.b.ym + seg * 17;
+            const double* yi = L.u.b.yi + seg * 17;
+            const double4* st = xs + j * 16;
+            const double2 cx = xc[j * NSEG + t];
+            double yn[NBAND];
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < NBAND; ++b) {
+                yn[b] = (yr[b] - ym[b]) * yi[b];
+                s += yn[b];
+            }
+            const double cy = s / NBAND;
+            double c2 = 0.0, cr = 0.0;
+#pragma unroll
+            for (int b = 0; b < NBAND; ++b) {
+                const double d = yn[b] - cy;
+                const double xn = (xr[b] - st[b].y) * st[b].z;
+                c2 = fma(d, d, c2);
+                cr = fma(d, xn - cx.x, cr);
+            }
+            acc += (cr * cx.y) / (sqrt(c2) + EPS);
+        }
+    }
+    return acc;
+}
+
 // PRE: the cell's test signal is given at 10 kHz (y10 + c n10, fp64: other
 // input rates, resampled by stoi_resample_kernel); otherwise the 16-kHz
-// output y is resampled in phase A.
-template <bool PRE>
+// output y is resampled in phase A.  EXT: extended STOI (xcol: the clean
+// side's column statistics), the same phase A and tile load.
+template <bool PRE, bool EXT = false>
 __device__ __forceinline__ void stoi_cells_body(StoiLds& L, const StoiArgs& a,
                                                 const double* __restrict__ coef,
-                                                const double* __restrict__ y10, int64_t n10) {
+                                                const double* __restrict__ y10, int64_t n10,
+                                                const double2* __restrict__ xcol = nullptr) {
     using namespace stoi;
     const int64_t c = blockIdx.x;
     const int tid = threadIdx.x;
@@ -923,7 +1055,7 @@ __device__ __forceinline__ void stoi_cells_body(StoiLds& L, const StoiArgs& a,
         stoi_phase_a<true>(L, nullptr, 0, 0, false, y10 + c * n10, nullptr,
                            a.btab + (int64_t)sig * a.NBLK * BT, a.meta[META * sig + 4], env, ts);
     else
-        stoi_phase_a<false>(L, a.y + a.y_offset[c], a.len, lag, a.clip != 0, nullptr, coef,
+        stoi_phase_a<false, EXT>(L, a.y + a.y_offset[c], a.len, lag, a.clip != 0, nullptr, coef,
                             a.btab + (int64_t)sig * a.NBLK * BT, a.meta[META * sig + 4], env, ts);
     __syncthreads();  // env rows of this workgroup are visible to it
     ts.mark(4);
@@ -956,6 +1088,10 @@ __device__ __forceinline__ void stoi_cells_body(StoiLds& L, const StoiArgs& a,
             }
         }
         __syncthreads();
+        if constexpr (EXT) {  // the plain correlations below are not reached
+            dsum += estoi_tile(L, j0, J, xs, xcol + (int64_t)sig * a.Jmax * NSEG);
+            continue;
+        }
         const int j = j0 + seg;
         if (j < J) {
 #pragma unroll 1
@@ -996,7 +1132,7 @@ __device__ __forceinline__ void stoi_cells_body(StoiLds& L, const StoiArgs& a,
     if (tid == 0) {
         double s = 0.0;
         for (int w = 0; w < NT / 64; ++w) s += L.red[w];
-        a.out[c] = s / ((double)J * NBAND);
+        a.out[c] = s / ((double)J * (EXT ? NSEG : NBAND));
     }
 #ifdef CSE_STOI_STAMPS
     ts.mark(5);
@@ -1023,6 +1159,22 @@ __global__ void __launch_bounds__(stoi::NT, 3) stoi_cells_pre_kernel(StoiArgs a,
                                                                   int64_t n10) {
     __shared__ StoiLds L;
     stoi_cells_body<true>(L, a, nullptr, y10, n10);
+}
+
+// extended STOI: the same two forms with the extended phase B
+__global__ void __launch_bounds__(stoi::NT, 3) estoi_cells_kernel(StoiArgs a,
+                                                               const double* __restrict__ coef,
+                                                               const double2* __restrict__ xcol) {
+    __shared__ StoiLds L;
+    stoi_cells_body<false, true>(L, a, coef, nullptr, 0, xcol);
+}
+
+__global__ void __launch_bounds__(stoi::NT, 3) estoi_cells_pre_kernel(StoiArgs a,
+                                                                   const double* __restrict__ y10,
+                                                                   int64_t n10,
+                                                                   const double2* __restrict__ xcol) {
+    __shared__ StoiLds L;
+    stoi_cells_body<true, true>(L, a, nullptr, y10, n10, xcol);
 }
 
 }  // namespace cse
@@ -1058,12 +1210,24 @@ extern "C" int64_t cse_stoi_scratch_bytes(int64_t n_cells, int64_t len) {
     return cse_stoi_scratch_bytes_sr(n_cells, len, 16000);
 }
 
-extern "C" int cse_stoi_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
-                                void* workspace, cse_stream_t stream) {
-    CSE_CHECK_ARG(clean && workspace, "cse_stoi_prepare: NULL clean/workspace");
-    CSE_CHECK_ARG(n_sig >= 1 && n_sig < 65536 && len >= 1, "cse_stoi_prepare: n_sig=%lld len=%lld",
+// extended STOI (include/cse_estoi.h): the workspace is stoi_layout's followed
+// by the clean side's column statistics, double2 [n_sig][Jmax][30]
+static int64_t estoi_xcol_bytes(const StoiLayout& L, int64_t n_sig) {
+    return align256(n_sig * L.Jmax * stoi::NSEG * 16);
+}
+
+extern "C" int64_t cse_estoi_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
+    if (n_sig < 1 || len < 1 || !stoi_rate_ok(sr, len)) return -1;
+    const StoiLayout L = stoi_layout(n_sig, len, sr);
+    return L.total + estoi_xcol_bytes(L, n_sig);
+}
+
+static int stoi_prepare_launch(const char* name, bool ext, const double* clean, int64_t n_sig,
+                               int64_t len, int sr, void* workspace, cse_stream_t stream) {
+    CSE_CHECK_ARG(clean && workspace, "%s: NULL clean/workspace", name);
+    CSE_CHECK_ARG(n_sig >= 1 && n_sig < 65536 && len >= 1, "%s: n_sig=%lld len=%lld", name,
                   (long long)n_sig, (long long)len);
-    CSE_CHECK_ARG(stoi_rate_ok(sr, len), "cse_stoi_prepare: sr=%d not supported", sr);
+    CSE_CHECK_ARG(stoi_rate_ok(sr, len), "%s: sr=%d not supported", name, sr);
     const StoiLayout L = stoi_layout(n_sig, len, sr);
     unsigned char* ws = (unsigned char*)workspace;
     hipStream_t st = (hipStream_t)stream;
@@ -1101,8 +1265,23 @@ extern "C" int cse_stoi_prepare(const double* clean, int64_t n_sig, int64_t len,
     if (L.Jmax > 0)
         hipLaunchKernelGGL(stoi_clean_stat_kernel, dim3(ceil_div(L.Jmax * 16, 256), (unsigned)n_sig),
                            dim3(256), 0, st, xtob, L.Mmax, L.Jmax, meta, xstat);
-    CSE_CHECK_LAUNCH("cse_stoi_prepare");
+    if (ext && L.Jmax > 0)
+        hipLaunchKernelGGL(stoi_clean_col_kernel,
+                           dim3(ceil_div(L.Jmax * stoi::NSEG, 256), (unsigned)n_sig), dim3(256), 0,
+                           st, (const double*)xtob, L.Mmax, L.Jmax, (const int*)meta,
+                           (const double4*)xstat, (double2*)(ws + L.total));
+    CSE_CHECK_LAUNCH(name);
     return CSE_OK;
+}
+
+extern "C" int cse_stoi_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
+                                void* workspace, cse_stream_t stream) {
+    return stoi_prepare_launch("cse_stoi_prepare", false, clean, n_sig, len, sr, workspace, stream);
+}
+
+extern "C" int cse_estoi_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
+                                 void* workspace, cse_stream_t stream) {
+    return stoi_prepare_launch("cse_estoi_prepare", true, clean, n_sig, len, sr, workspace, stream);
 }
 
 #ifdef CSE_STOI_STAMPS
@@ -1114,7 +1293,7 @@ extern "C" int cse_stoi_stamp_buffer(void* buf) {
 }
 #endif
 
-static int stoi_cells_launch(const char* name, const float* y, const int64_t* y_offset,
+static int stoi_cells_launch(const char* name, bool ext, const float* y, const int64_t* y_offset,
                              const int32_t* lag, const int32_t* sig_of, int64_t n_cells,
                              int64_t n_sig, int64_t len, int sr, int clip, const void* workspace,
                              void* scratch, double* stoi_out, cse_stream_t stream) {
@@ -1146,9 +1325,14 @@ static int stoi_cells_launch(const char* name, const float* y, const int64_t* y_
     a.scratch = (double*)scratch;
     a.out = stoi_out;
     hipStream_t st = (hipStream_t)stream;
+    const double2* xcol = (const double2*)(ws + L.total);  // extended workspaces only
     if (sr == 16000) {
-        hipLaunchKernelGGL(stoi_cells_kernel, dim3((unsigned)n_cells), dim3(stoi::NT), 0, st, a,
-                           a.coef);
+        if (ext)
+            hipLaunchKernelGGL(estoi_cells_kernel, dim3((unsigned)n_cells), dim3(stoi::NT), 0, st,
+                               a, a.coef, xcol);
+        else
+            hipLaunchKernelGGL(stoi_cells_kernel, dim3((unsigned)n_cells), dim3(stoi::NT), 0, st, a,
+                               a.coef);
     } else {
         // the cells' shifted, clipped outputs resampled to 10 kHz after their envelopes
         const Resamp r = resamp_for(sr, len);
@@ -1157,8 +1341,12 @@ static int stoi_cells_launch(const char* name, const float* y, const int64_t* y_
                            dim3(ceil_div(L.n10, 256), (unsigned)n_cells), dim3(256), 0, st, nullptr, y, y_offset, lag, clip, len,
                            (const double*)(ws + L.hgen), 2 * r.half + 1, r.up, r.down, r.pre_pad,
                            r.pre_rm, L.n10, y10);
-        hipLaunchKernelGGL(stoi_cells_pre_kernel, dim3((unsigned)n_cells), dim3(stoi::NT), 0, st, a,
-                           (const double*)y10, L.n10);
+        if (ext)
+            hipLaunchKernelGGL(estoi_cells_pre_kernel, dim3((unsigned)n_cells), dim3(stoi::NT), 0,
+                               st, a, (const double*)y10, L.n10, xcol);
+        else
+            hipLaunchKernelGGL(stoi_cells_pre_kernel, dim3((unsigned)n_cells), dim3(stoi::NT), 0, st,
+                               a, (const double*)y10, L.n10);
     }
     CSE_CHECK_LAUNCH(name);
     return CSE_OK;
@@ -1168,7 +1356,7 @@ extern "C" int cse_stoi_cells(const float* y, const int64_t* y_offset, const int
                               const int32_t* sig_of, int64_t n_cells, int64_t n_sig, int64_t len,
                               int clip, const void* workspace, void* scratch, double* stoi_out,
                               cse_stream_t stream) {
-    return stoi_cells_launch("cse_stoi_cells", y, y_offset, lag, sig_of, n_cells, n_sig, len,
+    return stoi_cells_launch("cse_stoi_cells", false, y, y_offset, lag, sig_of, n_cells, n_sig, len,
                              16000, clip, workspace, scratch, stoi_out, stream);
 }
 
@@ -1176,6 +1364,14 @@ extern "C" int cse_stoi_cells_sr(const float* y, const int64_t* y_offset, const 
                                  const int32_t* sig_of, int64_t n_cells, int64_t n_sig,
                                  int64_t len, int sr, int clip, const void* workspace,
                                  void* scratch, double* stoi_out, cse_stream_t stream) {
-    return stoi_cells_launch("cse_stoi_cells_sr", y, y_offset, lag, sig_of, n_cells, n_sig, len,
-                             sr, clip, workspace, scratch, stoi_out, stream);
+    return stoi_cells_launch("cse_stoi_cells_sr", false, y, y_offset, lag, sig_of, n_cells, n_sig,
+                             len, sr, clip, workspace, scratch, stoi_out, stream);
+}
+
+extern "C" int cse_estoi_cells(const float* y, const int64_t* y_offset, const int32_t* lag,
+                               const int32_t* sig_of, int64_t n_cells, int64_t n_sig, int64_t len,
+                               int sr, int clip, const void* workspace, void* scratch,
+                               double* estoi, cse_stream_t stream) {
+    return stoi_cells_launch("cse_estoi_cells", true, y, y_offset, lag, sig_of, n_cells, n_sig, len,
+                             sr, clip, workspace, scratch, estoi, stream);
 }

@@ -18,6 +18,13 @@ finalize_enhanced (speech_enhancement_comparison.py:92-106).  The sweep runs
 at the reference's working rate, 16 kHz (:381), resampled to 10 kHz inside the
 cell kernel; other rates (1-768 kHz, 10 kHz unresampled) go through a generic
 fp64 resampler first (cse_stoi_cells_sr).  There is no CPU fallback.
+
+extended=True scores extended STOI (Jensen & Taal 2016; pystoi's
+``extended=True``, which the reference never passes) through cse_estoi_prepare /
+cse_estoi_cells: the same clean side plus per-(segment, frame) column
+statistics, the same resampling, silent-frame removal and band envelopes, then
+the row- and column-normalised correlation defined in include/cse_estoi.h
+(no jitter; norm + eps divisors).
 """
 
 import math
@@ -44,9 +51,10 @@ def _gpu_visible():
 
 
 class StoiPlan:
-    """Clean side of STOI for S equal-length signals (clean: [S, L] f64 cuda)."""
+    """Clean side of STOI for S equal-length signals (clean: [S, L] f64 cuda);
+    extended=True: of extended STOI, which the plan then scores."""
 
-    def __init__(self, clean, sr=STOI_SR):
+    def __init__(self, clean, sr=STOI_SR, extended=False):
         if not _gpu_visible():
             raise _lib.CseError("no GPU visible: the HIP engine has no CPU fallback")
         self.lib = _lib.load()
@@ -56,12 +64,16 @@ class StoiPlan:
         self.S, self.L = clean.shape
         self.clean = clean
         self.sr = int(sr)
-        nbytes = int(self.lib.cse_stoi_workspace_bytes_sr(self.S, self.L, self.sr))
+        self.extended = bool(extended)
+        size_fn, prepare, name = (
+            (self.lib.cse_estoi_workspace_bytes, self.lib.cse_estoi_prepare, "cse_estoi_prepare")
+            if self.extended else
+            (self.lib.cse_stoi_workspace_bytes_sr, self.lib.cse_stoi_prepare, "cse_stoi_prepare"))
+        nbytes = int(size_fn(self.S, self.L, self.sr))
         if nbytes < 0:
             raise NotImplementedError(f"STOI: sample rate {sr} not supported (1000-768000 Hz)")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=clean.device)
-        _lib.check(self.lib.cse_stoi_prepare(_ptr(clean), self.S, self.L, sr, _ptr(self.ws),
-                                             _stream()), "cse_stoi_prepare")
+        _lib.check(prepare(_ptr(clean), self.S, self.L, sr, _ptr(self.ws), _stream()), name)
         self._scratch = None
 
     def _scratch_for(self, n):
@@ -133,7 +145,9 @@ class StoiPlan:
             args = (_ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]),
                     m, self.S, self.L)
             tail = (1 if clip else 0, _ptr(self.ws), _ptr(scratch), _ptr(out[s:]), _stream())
-            if self.sr == STOI_SR:
+            if self.extended:
+                _lib.check(self.lib.cse_estoi_cells(*args, self.sr, *tail), "cse_estoi_cells")
+            elif self.sr == STOI_SR:
                 _lib.check(self.lib.cse_stoi_cells(*args, *tail), "cse_stoi_cells")
             else:
                 _lib.check(self.lib.cse_stoi_cells_sr(*args, self.sr, *tail), "cse_stoi_cells_sr")
@@ -144,15 +158,16 @@ class StoiPlan:
         return self.score_async(y, y_offset, sig_of, lag, clip).cpu().numpy()
 
 
-def stoi(x, y, fs_sig):
-    """pystoi ``stoi(x, y, fs_sig, extended=False)`` on the device."""
+def stoi(x, y, fs_sig, extended=False):
+    """pystoi ``stoi(x, y, fs_sig, extended=False)`` on the device; with
+    extended=True, extended STOI as include/cse_estoi.h defines it."""
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     if x.shape != y.shape:
         raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
     if x.ndim != 1 or x.size == 0:
         raise ValueError("stoi expects non-empty 1-D signals")
-    plan = StoiPlan(torch.as_tensor(x).cuda().view(1, -1), fs_sig)
+    plan = StoiPlan(torch.as_tensor(x).cuda().view(1, -1), fs_sig, extended=extended)
     yd = torch.as_tensor(y.astype(np.float32)).cuda()
     v = float(plan.score(yd, [0], [0], clip=False)[0])
     if math.isnan(v):
@@ -160,12 +175,13 @@ def stoi(x, y, fs_sig):
     return v
 
 
-def calculate_stoi(clean_reference, test_audio, sr):
+def calculate_stoi(clean_reference, test_audio, sr, extended=False):
     """evaluation_metrics.calculate_stoi (:30-36): trim to the common length,
-    None on failure."""
+    None on failure.  extended=True scores extended STOI the same way."""
     try:
         n = min(len(clean_reference), len(test_audio))
-        return stoi(np.asarray(clean_reference)[:n], np.asarray(test_audio)[:n], sr)
+        return stoi(np.asarray(clean_reference)[:n], np.asarray(test_audio)[:n], sr,
+                    extended=extended)
     except (NotImplementedError, _lib.CseError):
         raise  # no device / unsupported: not a score failure
     except Exception as e:  # the reference's catch-all

@@ -33,6 +33,11 @@ Each cell is scored like finalize_enhanced (:92-106): its output is aligned
 to the clean reference by the cross-correlation lag (on the device,
 cse_xcorr_lag), length-matched, checked for finiteness and clipped, then
 calculate_snr and calculate_stoi.
+
+extended=True (run_grid, optimize_parameters, run_sweep; stoi="extended" in
+engine_compute) scores extended STOI in place of STOI (cse_estoi_cells,
+include/cse_estoi.h): the STOI column and every stoi field then hold ESTOI, and
+the selection and its tolerance are the STOI objective's.
 """
 
 import math
@@ -269,7 +274,7 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True)
     """Device compute of the cells ``ids``: per-cell (sse, snr, finite, stoi,
     lag, xstatus), scored after finalize_enhanced's alignment (align=False: at
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
-    waveforms are kept).
+    waveforms are kept); stoi="extended" fills it with extended STOI.
 
     clean/noisy: lists of 1-D float arrays (host) indexed by pair.  Pairs are
     batched by length (the engine's signal batches are rectangular), and, when
@@ -286,6 +291,8 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True)
     and trims the cache back to
     the caller's size on return."""
     from .engine import Engine
+    if not (isinstance(stoi, bool) or stoi == "extended"):
+        raise ValueError(f"stoi={stoi!r}: True, False or 'extended'")
     own = engine is None
     eng = engine or Engine()
     size0 = eng.plan_cache_size
@@ -362,7 +369,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
             cl = torch.as_tensor(np.stack([np.asarray(clean[p], np.float64) for p in pairs])).cuda()
             cpow = np.array([float(np.dot(np.asarray(clean[p], np.float64),
                                           np.asarray(clean[p], np.float64))) for p in pairs])
-            splan = StoiPlan(cl) if stoi else None
+            splan = StoiPlan(cl, extended=(stoi == "extended")) if stoi else None
             state = {}
 
             def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, state=state):
@@ -560,12 +567,15 @@ def select_best(specs, table, objective="snr", tol=None):
     return best
 
 
-def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr"):
+def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
+             extended=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
     gets the full table (all_gather); the selection is the deterministic
-    sequential scan, identical on every rank."""
+    sequential scan, identical on every rank.  extended=True: the default
+    compute (engine_compute) scores extended STOI into the stoi column; a
+    compute function given by the caller scores what it scores."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
@@ -573,6 +583,9 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     lengths = [len(x) for x in noisy]
     rank_of, _ = assign_shards(specs, lengths, world)
     ids = np.nonzero(rank_of == rank)[0]
+    if compute is None and extended:
+        def compute(clean, noisy, specs, ids):
+            return engine_compute(clean, noisy, specs, ids, stoi="extended")
     compute = compute or engine_compute
     vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, NCOL))
     if not dist_on and len(ids) == len(specs):  # one process, every cell in order: no gather
@@ -589,9 +602,9 @@ def _snr_baseline(c, n):
     return math.inf if err == 0 else float(10 * np.log10(np.sum(c[:m] ** 2) / (err + 1e-10)))
 
 
-def _device_stoi(clean, test, sr):
+def _device_stoi(clean, test, sr, extended=False):
     from .metrics import calculate_stoi
-    return calculate_stoi(clean, test, sr)
+    return calculate_stoi(clean, test, sr, extended=extended)
 
 
 def _opt(v):
@@ -599,14 +612,17 @@ def _opt(v):
 
 
 def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_ranges=None,
-                        compute=None, stoi_fn=None):
+                        compute=None, stoi_fn=None, extended=False):
     """Single-pair, single-algorithm mirror of the reference's
     optimize_parameters (speech_enhancement_comparison.py:109-252), scored by
     STOI and SNR: returns {'stoi': {'score', 'params', 'cell', 'snr'},
     'snr': {'score', 'params', 'cell', 'stoi'}, 'baseline': {'stoi', 'snr'},
     'improvements': {'stoi', 'snr'}, 'table'}; raises ValueError like :233-235
     when no cell produced a finite output.  The 'stoi' entry is None when no
-    cell has a STOI value (a compute function that does not score STOI)."""
+    cell has a STOI value (a compute function that does not score STOI).
+    extended=True: the cells and the baseline are scored with extended STOI
+    (every 'stoi' value above is then ESTOI) and the result carries
+    'extended': True."""
     from .engine import canonical_algo
     if sr != 16000:
         raise ValueError("the device path runs at 16 kHz (prepare_pair resamples to 16 kHz)")
@@ -615,7 +631,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     specs = job_specs(1, [alg], grids)
     clean = [np.asarray(clean_reference, np.float64)]
     noisy = [np.asarray(noisy_audio, np.float64)]
-    table, best = run_grid(clean, noisy, specs, compute=compute)
+    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -624,9 +640,14 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
                    "stoi": _opt(table[cid, 3])},
            "baseline": {"snr": base}, "improvements": {"snr": score - base}, "table": table,
            "stoi": None}
+    if extended:
+        out["extended"] = True
     sid, sscore = select_best(specs, table, "stoi")[(0, alg)]
     if sid >= 0:
-        bstoi = (stoi_fn or _device_stoi)(clean[0], noisy[0], sr) or 0  # :115 "or 0"
+        if stoi_fn is None and extended:
+            bstoi = _device_stoi(clean[0], noisy[0], sr, extended=True) or 0
+        else:
+            bstoi = (stoi_fn or _device_stoi)(clean[0], noisy[0], sr) or 0  # :115 "or 0"
         out["stoi"] = {"score": sscore, "params": dict(specs[sid][2]), "cell": int(sid),
                        "snr": float(table[sid, 1])}
         out["baseline"]["stoi"] = bstoi
@@ -635,14 +656,17 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
 
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
-              group=None, device=None):
+              group=None, device=None, extended=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
     (pair, algorithm) selected by the sequential tolerance scan, their
     waveforms written as results_{alg}/{stem}_{alg}_optimized_stoi.wav (the
     reference's name, :303) and ..._optimized_snr.wav, and the summary files
-    (results.write_summary) under results_summary/.  Rank 0 writes."""
+    (results.write_summary) under results_summary/.  Rank 0 writes.
+    extended=True: scored and selected by extended STOI; the rows' stoi_* fields
+    then hold ESTOI, each row carries "stoi_extended": True, and the file names
+    stay the same."""
     import torch
     import torch.distributed as dist
     from . import results
@@ -651,7 +675,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     grids = grids or ALGORITHM_GRIDS
     algorithms = list(algorithms or grids)
     specs = job_specs(len(noisy), algorithms, grids)
-    table, best = run_grid(clean, noisy, specs, group=group, device=device)
+    table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
@@ -663,7 +687,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         n = np.asarray(noisy[pair], np.float64)
         snr_noisy = _snr_baseline(c, n)
         m = min(len(c), len(n))
-        plan = StoiPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
+        plan = StoiPlan(torch.as_tensor(c[:m]).cuda().view(1, -1), extended=extended)
         nf = torch.as_tensor(n[:m].astype(np.float32)).cuda()
         stoi_noisy = _opt(plan.score(nf, [0], [0], clip=False)[0])
         x = torch.as_tensor(n).cuda().view(1, -1)
@@ -688,5 +712,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                 stoi_best=None if sid < 0 else float(sscore),
                 stoi_params=None if sid < 0 else specs[sid][2],
                 snr_stoiopt=None if sid < 0 else float(table[sid, 1])))
+            if extended:
+                rows[-1]["stoi_extended"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
     return rows

@@ -1,10 +1,14 @@
 """Throughput of the device STOI (cse_stoi_cells) on 10-s cells (GPU box).
 
-    python tools/bench_stoi.py [--cells N --pairs P --reps R]
+    python tools/bench_stoi.py [--cells N --pairs P --reps R] [--extended]
 
 Cells are noisy versions of P synthetic 10-s clean signals (random gains and
 lags, some outputs beyond [-1, 1] so the clip path runs).  Prints one JSON
 line: cells/s, ms per launch, and the per-cell fp64 work estimate.
+
+--extended also times extended STOI (cse_estoi_cells) on the same cells in the
+same process, its launches alternating with the plain ones, and adds
+estoi_ms_per_launch, estoi_over_stoi and estoi_mean to the line.
 """
 
 import argparse
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--extended", action="store_true")
     a = ap.parse_args()
     pairs = [make_pair(100 + i, a.seconds) for i in range(a.pairs)]
     clean = torch.as_tensor(np.stack([c for c, _ in pairs])).cuda()
@@ -44,24 +49,43 @@ def main():
     prep_ms = (time.perf_counter() - t0) * 1e3
     off = np.arange(a.cells, dtype=np.int64) * L
     plan.score_async(y, off, sig, lag=lag)  # warm-up (scratch allocation)
+    xplan = None
+    if a.extended:
+        xplan = StoiPlan(clean, extended=True)
+        xplan.score_async(y, off, sig, lag=lag)
     torch.cuda.synchronize()
-    times = []
-    for _ in range(a.reps):
+
+    def timed(pl):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        out = plan.score_async(y, off, sig, lag=lag)
+        o = pl.score_async(y, off, sig, lag=lag)
         e1.record()
         torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
+        return e0.elapsed_time(e1), o
+
+    times, xtimes = [], []
+    for _ in range(a.reps):
+        t, out = timed(plan)
+        times.append(t)
+        if xplan is not None:
+            t, xout = timed(xplan)
+            xtimes.append(t)
     ms = float(np.median(times))
     v = out.cpu().numpy()
     if os.environ.get("CSE_STOI_DUMP"):  # per-cell scores, to compare resampler paths
         np.save(os.environ["CSE_STOI_DUMP"], v)
     if not os.environ.get("CSE_BENCH_NOCHECK"):
         assert os.environ.get("CSE_BENCH_NOCHECK") or np.isfinite(v).all()
-    print(json.dumps({"what": "cse_stoi_cells", "cells": a.cells, "clip_s": a.seconds,
-                      "ms_per_launch": ms, "cells_per_s": a.cells / (ms / 1e3),
-                      "prepare_ms_incl_first_launch": prep_ms, "stoi_mean": float(v.mean())}))
+    line = {"what": "cse_stoi_cells", "cells": a.cells, "clip_s": a.seconds,
+            "ms_per_launch": ms, "cells_per_s": a.cells / (ms / 1e3),
+            "prepare_ms_incl_first_launch": prep_ms, "stoi_mean": float(v.mean())}
+    if xplan is not None:
+        xv = xout.cpu().numpy()
+        assert np.isfinite(xv).all()
+        xms = float(np.median(xtimes))
+        line.update(estoi_ms_per_launch=xms, estoi_over_stoi=xms / ms, estoi_mean=float(xv.mean()),
+                    ms_all=[round(t, 4) for t in times], estoi_ms_all=[round(t, 4) for t in xtimes])
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":
