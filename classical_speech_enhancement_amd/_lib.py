@@ -1,5 +1,5 @@
-"""ctypes binding of libcse.so (the C ABI declared in include/cse.h and
-include/cse_estoi.h).
+"""ctypes binding of libcse.so (the C ABI declared in include/cse.h,
+include/cse_estoi.h and include/cse_mcra.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -18,7 +18,7 @@ CSE_OK = 0
 # NOISE_JOB_DTYPE == cse_noise_job_t, NoiseParams == cse_noise_params_t)
 ABI_VERSION = 5
 ALGO = {"NONE": -1, "SS": 0, "WIENER": 1, "MMSE": 2, "OMLSA": 3}
-NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2}
+NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "mcra": 3}
 
 # numpy mirror of cse_cell_t (include/cse.h) — 96 bytes
 CELL_DTYPE = np.dtype([
@@ -47,6 +47,16 @@ class NoiseParams(ctypes.Structure):
 
 assert ctypes.sizeof(NoiseParams) == 48
 
+
+class McraParams(ctypes.Structure):
+    """cse_mcra_params_t (include/cse_mcra.h): the MCRA tracker's parameters."""
+    _fields_ = [("alpha_s", ctypes.c_double), ("alpha_d", ctypes.c_double),
+                ("alpha_p", ctypes.c_double), ("delta", ctypes.c_double),
+                ("window_frames", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(McraParams) == 40
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -59,6 +69,8 @@ EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_stoi_cells_sr")
 # include/cse_estoi.h (extended STOI), a header of its own: EXPORTS is what cse.h declares
 EXPORTS_ESTOI = ("cse_estoi_workspace_bytes", "cse_estoi_prepare", "cse_estoi_cells")
+# include/cse_mcra.h (MCRA noise tracking), likewise
+EXPORTS_MCRA = ("cse_mcra_default_params", "cse_noise_mcra")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -148,6 +160,10 @@ def load(path=LIB_PATH):
     lib.cse_estoi_prepare.argtypes = [P, i64, i64, i32, P, P]
     lib.cse_estoi_cells.restype = i32
     lib.cse_estoi_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
+    lib.cse_mcra_default_params.restype = None
+    lib.cse_mcra_default_params.argtypes = [P]
+    lib.cse_noise_mcra.restype = i32
+    lib.cse_noise_mcra.argtypes = [P, i64, i32, i32, P, f64, P, P]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

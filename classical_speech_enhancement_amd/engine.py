@@ -21,9 +21,9 @@ import torch
 from . import _lib
 # the planning names other modules and the tests import from here stay importable
 from .layout import (ALGO_COST, ALGOS, ALIGN_CORR_SAMPLES, ALIGN_MAX_LAG,  # noqa: F401
-                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, SHORT, PlanLayout, Ref,
-                     canonical_algo, n_frames, noise_key, noise_params, pack_waves, route,
-                     route_slots, specs_by_n_fft)
+                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, MCRA_DEFAULTS, SHORT, PlanLayout,
+                     Ref, canonical_algo, mcra_params, mcra_values, n_frames, noise_key,
+                     noise_params, pack_waves, route, route_slots, specs_by_n_fft)
 
 
 def _ptr(t):
@@ -73,8 +73,22 @@ class Engine:
         constructor parameters (min_frames, max_fraction, floor_rel,
         adaptive_short, window_size, smoothing_factor; noise_estimation.py:12-13,
         :60).  true_noise: P is the power of STFT(noisy - clean) over the
-        shorter length, fit to ``frames`` (default T') frames (:149-153)."""
+        shorter length, fit to ``frames`` (default T') frames (:149-153).
+        mcra: cse_noise_mcra (include/cse_mcra.h) -> [S, T, B] at any T; params
+        are alpha_s, alpha_d, alpha_p, delta, window_frames."""
         S, Tp, B = P.shape
+        if method == "mcra":
+            if frames is not None and int(frames) != Tp:
+                raise ValueError("frames applies to true_noise only")
+            unknown = set(params) - set(MCRA_DEFAULTS)
+            if unknown:
+                raise TypeError(f"mcra takes no parameter {sorted(unknown)[0]!r}")
+            prm = mcra_params(mcra_values(params))
+            if out is None:
+                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
+            _lib.check(self.lib.cse_noise_mcra(_ptr(P), S, Tp, B, ctypes.byref(prm), float(eps),
+                                               _ptr(out), _stream()), "cse_noise_mcra")
+            return out
         T = Tp if frames is None else int(frames)
         code = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "simple": 0}[method]
         static = method == "percentile" or (T < 5 and method != "true_noise")
@@ -261,7 +275,7 @@ class GridPlan:
         if isinstance(a, Ref):
             buf = getattr(self, a.buf)
             return _at(buf[hop] if isinstance(buf, dict) else buf, a.off)
-        return ctypes.byref(a) if isinstance(a, _lib.NoiseParams) else a
+        return ctypes.byref(a) if isinstance(a, (_lib.NoiseParams, _lib.McraParams)) else a
 
     def enhance(self):
         """THE HOT PATH launch: every cell of this n_fft, one kernel."""

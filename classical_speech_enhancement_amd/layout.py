@@ -68,10 +68,44 @@ def n_frames(length, hop):
     return 1 + int(length) // int(hop)
 
 
+# the MCRA tracker's parameters (include/cse_mcra.h; Cohen & Berdugo 2002, the
+# paper's values for n_fft 512 / hop 128 at 16 kHz).  Cell params carry them
+# as mcra_<name>.
+MCRA_DEFAULTS = {"alpha_s": 0.8, "alpha_d": 0.95, "alpha_p": 0.2, "delta": 5.0,
+                 "window_frames": 125}
+
+
+def mcra_values(params, prefix=""):
+    """(alpha_s, alpha_d, alpha_p, delta, window_frames) read from ``params``
+    under prefix + name, defaults where absent; raises ValueError for what
+    cse_noise_mcra refuses."""
+    a_s, a_d, a_p, delta = (float(params.get(prefix + k, MCRA_DEFAULTS[k]))
+                            for k in ("alpha_s", "alpha_d", "alpha_p", "delta"))
+    w = params.get(prefix + "window_frames", MCRA_DEFAULTS["window_frames"])
+    for name, a in (("alpha_s", a_s), ("alpha_d", a_d), ("alpha_p", a_p)):
+        if not 0.0 <= a < 1.0:
+            raise ValueError(f"mcra {name}={a} not in [0, 1)")
+    if not delta > 0.0:
+        raise ValueError(f"mcra delta={delta} not > 0")
+    if w != int(w) or not 2 <= int(w) < 2**31:
+        raise ValueError(f"mcra window_frames={w} not an integer >= 2")
+    return (a_s, a_d, a_p, delta, int(w))
+
+
+def mcra_params(values):
+    """cse_mcra_params_t from mcra_values' tuple."""
+    prm = _lib.McraParams()
+    prm.alpha_s, prm.alpha_d, prm.alpha_p, prm.delta, prm.window_frames = values
+    return prm
+
+
 def noise_key(alg, params, T):
     """Which noise PSD array a cell reads, mirroring each algorithm's pipeline.
 
-    Returns (method, pct, eps, expand, mu, inverse):
+    Returns (method, pct, eps, expand, mu, inverse); pct is the estimator's
+    parameter slot: the percentile, or for mcra the mcra_values tuple
+    (noise_percentile does not enter: cells that differ only in it share one
+    estimate):
       - every algorithm estimates with the eps it passes (ss/wiener/omlsa 1e-10,
         mmse 1e-12: spectral_subtractor.py:17, wiener_filter.py:23, mmse.py:17,
         advanced_mmse.py:26);
@@ -82,6 +116,9 @@ def noise_key(alg, params, T):
         advanced_mmse.py:54-55), which ZERO-PADS frames 1..T-1 — frame 0 sees
         the estimate, later frames see 0 (SS) or, after OMLSA's smoothing,
         mu**t times it;
+      - mcra (no counterpart in the reference) is time-varying and takes
+        min_tracking's place in each pipeline: smoothed by mmse/omlsa, inverted
+        with the algorithm's eps for Wiener/MMSE/OMLSA, as it is for SS;
       - mmse/omlsa smooth any time-varying estimate except true_noise
         (mmse.py:48-54, advanced_mmse.py:60-66); mu=None means no smoothing;
       - inverse: Wiener/MMSE/OMLSA read 1/max(N, eps) (their in-loop floor,
@@ -91,8 +128,11 @@ def noise_key(alg, params, T):
     """
     code, eps, _ = ALGOS[alg]
     method = params["noise_method"]
+    mcra = mcra_values(params, "mcra_") if method == "mcra" else None  # validated at any T
     if T < 5:
         method, pct = "simple", None
+    elif mcra is not None:  # time-varying, like min_tracking
+        pct = mcra
     elif method == "percentile":
         pct = float(params["noise_percentile"])
     elif method in ("min_tracking", "true_noise"):
@@ -144,6 +184,8 @@ def specs_by_n_fft(S, L, specs, with_clean, want_g):
         if not 0 <= int(sig) < S:
             raise ValueError(f"signal index {sig} out of range")
         ck = (alg, hop, nf, p["noise_method"])
+        if ck[3] == "mcra":  # and per distinct parameter set
+            ck += mcra_values(p, "mcra_")
         if ck not in checked:  # per distinct (algorithm, hop, n_fft, method)
             r = route(nf, hop)
             if r is None:
@@ -258,6 +300,8 @@ class PlanLayout:
         for (_, _, alg, p) in self.items:
             hop = p["hop_length"]
             ck = (alg, hop, p["noise_method"], p.get("noise_percentile"), p.get("noise_mu"))
+            if ck[2] == "mcra":
+                ck += mcra_values(p, "mcra_")
             k = key_cache.get(ck)
             if k is None:
                 k = key_cache[ck] = (hop, noise_key(alg, p, n_frames(L, hop)))
@@ -346,6 +390,9 @@ class PlanLayout:
             if method == "simple":
                 calls.append(("cse_noise_estimate",
                               (0, P, S, T, B, 25.0, float(eps), raw(b), ws)))
+            elif method == "mcra":  # one call per (parameter set, eps)
+                calls.append(("cse_noise_mcra",
+                              (P, S, T, B, mcra_params(pct), float(eps), raw(b))))
             elif method == "true_noise":
                 prm = noise_params(src_frames=self.ptrue_shape[hop][1])
                 calls.append(("cse_noise_estimate_ex",

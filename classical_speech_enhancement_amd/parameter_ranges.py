@@ -58,6 +58,18 @@ ALGORITHM_GRIDS = {
 }
 
 
+def grids_with_noise_methods(methods, grids=None):
+    """Copies of the grids (default ALGORITHM_GRIDS) with the noise_method axis
+    replaced by ``methods``, e.g. ("percentile", "min_tracking", "mcra"): for
+    search.job_specs / run_grid / run_sweep (grids=...).  The default grids,
+    and so their cell ids, stay as they are."""
+    methods = list(methods)
+    if not methods:
+        raise ValueError("no noise method given")
+    return {alg: {k: (list(methods) if k == "noise_method" else list(v)) for k, v in g.items()}
+            for alg, g in (grids or ALGORITHM_GRIDS).items()}
+
+
 def grid_cells(ranges):
     """Param dicts in the reference's enumeration order."""
     names = list(ranges)

@@ -11,12 +11,17 @@ libcse.so (STFT, estimator and fused gain+ISTFT kernels), computed in fp32 on
 the device (fp64 analysis), within the 1e-5 relative tolerance of the
 north-star.  There is no CPU fallback: without the built library or a GPU
 these raise.
+
+One estimator goes beyond the reference: noise_method="mcra" (minima-controlled
+recursive averaging, include/cse_mcra.h).  The four algorithm plugins take its
+parameters as a trailing keyword mcra={alpha_s, alpha_d, alpha_p, delta,
+window_frames} (defaults: the paper's); every other call means what it meant.
 """
 
 import numpy as np
 import torch
 
-from .engine import NOISE_PARAM_KEYS, Engine, n_frames
+from .engine import MCRA_DEFAULTS, NOISE_PARAM_KEYS, Engine, n_frames
 
 _ENGINE = None
 
@@ -42,7 +47,12 @@ def _dev(x):
     return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).cuda().view(1, -1)
 
 
-def _single(alg, noisy, clean, params, rule):
+def _single(alg, noisy, clean, params, rule, mcra=None):
+    if mcra:  # the tracker's parameters ride in the cell params as mcra_<name>
+        unknown = set(mcra) - set(MCRA_DEFAULTS)
+        if unknown:
+            raise TypeError(f"mcra takes no parameter {sorted(unknown)[0]!r}")
+        params.update(("mcra_" + k, v) for k, v in mcra.items())
     x = _mono(noisy, rule)
     if x.size == 0:  # the reference's reflect padding of an empty signal raises
         raise ValueError("can't extend empty axis 0 using modes other than 'constant' or 'empty'")
@@ -67,36 +77,37 @@ def _single(alg, noisy, clean, params, rule):
 
 
 def spectral_subtraction(noisy_audio, sr, alpha, beta, n_fft, hop_length, noise_percentile,
-                         noise_method, clean_audio=None):
+                         noise_method, clean_audio=None, mcra=None):
     return _single("spectralSubtractor", noisy_audio, clean_audio,
                    dict(alpha=alpha, beta=beta, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method),
-                   "shorter")
+                   "shorter", mcra)
 
 
 def wiener_filter(noisy_audio, sr, n_fft, hop_length, alpha, gain_floor, noise_percentile,
-                  noise_method, clean_audio=None):
+                  noise_method, clean_audio=None, mcra=None):
     return _single("wiener", noisy_audio, clean_audio,
                    dict(alpha=alpha, gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
-                        noise_percentile=noise_percentile, noise_method=noise_method), "axis1")
+                        noise_percentile=noise_percentile, noise_method=noise_method), "axis1",
+                   mcra)
 
 
 def mmse(noisy_audio, sr, alpha, ksi_min, gain_min, gain_max, n_fft, hop_length,
          noise_percentile, noise_method, noise_mu=0.98, clean_audio=None, log=True,
-         log_every=50):
+         log_every=50, mcra=None):
     return _single("mmse", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, gain_min=gain_min, gain_max=gain_max,
                         n_fft=n_fft, hop_length=hop_length, noise_percentile=noise_percentile,
-                        noise_method=noise_method, noise_mu=noise_mu), "axis1")
+                        noise_method=noise_method, noise_mu=noise_mu), "axis1", mcra)
 
 
 def advanced_mmse(noisy_audio, sr, n_fft, hop_length, alpha, ksi_min, q, noise_mu, gain_floor,
-                  noise_percentile, noise_method, clean_audio=None, v_max=80.0):
+                  noise_percentile, noise_method, clean_audio=None, v_max=80.0, mcra=None):
     return _single("omlsa", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, q=q, noise_mu=noise_mu,
                         gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method,
-                        v_max=v_max), "shorter")
+                        v_max=v_max), "shorter", mcra)
 
 
 def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win_length=None,
@@ -109,7 +120,11 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
     max_fraction, floor_rel, adaptive_short, window_size, smoothing_factor),
     while estimate() reads eps and clean_audio from **kwargs only (:199-210):
     eps defaults to 1e-10 (percentile, min_tracking) / 1e-12 (true_noise), the
-    T < 5 fallback reads eps from the merged dict (:191-195)."""
+    T < 5 fallback reads eps from the merged dict (:191-195).
+
+    method="mcra" (not in the reference; include/cse_mcra.h) returns (B,T):
+    alpha_s, alpha_d, alpha_p, delta and window_frames come from the merged
+    dict, eps from **kwargs (default 1e-10)."""
     if window != "hann" or not center or pad_mode != "reflect" or (win_length or n_fft) != n_fft:
         raise NotImplementedError("only hann/center/reflect/win_length=n_fft is implemented")
     full = dict(estimator_params or {})
@@ -134,6 +149,11 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
     if method == "min_tracking":
         _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
         N = eng.noise_estimate("min_tracking", P, eps=kwargs.get("eps", 1e-10), **ctor)
+        return N[0].cpu().numpy().astype(np.float64).T
+    if method == "mcra":
+        _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
+        N = eng.noise_estimate("mcra", P, eps=kwargs.get("eps", 1e-10),
+                               **{k: full[k] for k in MCRA_DEFAULTS if k in full})
         return N[0].cpu().numpy().astype(np.float64).T
     if method == "true_noise":
         clean = kwargs.get("clean_audio")
