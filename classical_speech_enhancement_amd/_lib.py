@@ -1,5 +1,5 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
-include/cse_estoi.h and include/cse_mcra.h).
+include/cse_estoi.h, include/cse_mcra.h and include/cse_segsnr.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -71,6 +71,9 @@ EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
 EXPORTS_ESTOI = ("cse_estoi_workspace_bytes", "cse_estoi_prepare", "cse_estoi_cells")
 # include/cse_mcra.h (MCRA noise tracking), likewise
 EXPORTS_MCRA = ("cse_mcra_default_params", "cse_noise_mcra")
+# include/cse_segsnr.h (segmental and frequency-weighted segmental SNR), likewise
+EXPORTS_SEGSNR = ("cse_segsnr_workspace_bytes", "cse_segsnr_prepare", "cse_segsnr_scratch_bytes",
+                  "cse_segsnr_cells")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -164,6 +167,14 @@ def load(path=LIB_PATH):
     lib.cse_mcra_default_params.argtypes = [P]
     lib.cse_noise_mcra.restype = i32
     lib.cse_noise_mcra.argtypes = [P, i64, i32, i32, P, f64, P, P]
+    lib.cse_segsnr_workspace_bytes.restype = i64
+    lib.cse_segsnr_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cse_segsnr_prepare.restype = i32
+    lib.cse_segsnr_prepare.argtypes = [P, i64, i64, i32, P, P]
+    lib.cse_segsnr_scratch_bytes.restype = i64
+    lib.cse_segsnr_scratch_bytes.argtypes = [i64, i64, i32]
+    lib.cse_segsnr_cells.restype = i32
+    lib.cse_segsnr_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P, P]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

@@ -1,0 +1,681 @@
+// Segmental SNR and frequency-weighted segmental SNR (include/cse_segsnr.h) on
+// device.
+//
+// One workgroup per cell, one wave per frame.  The frames overlap by 75 %, so
+// the cell's test signal (shifted by its lag, clipped) and the f32 clean
+// samples are staged in LDS a chunk of FCH frames at a time; the last
+// W - hop samples of a chunk are carried over inside LDS, so each sample
+// comes from memory once per cell.  (Fetching the next chunk into registers
+// under the transforms was tried: 34 spilled VGPRs, 11.3 against 7.4 ms.)
+//
+// The NFFT-point transform of the real, zero-padded windowed frame f is an
+// H-point complex transform (H = NFFT / 2) of z[n] = f[2n] + i f[2n+1] plus the
+// real-FFT split.  z has W / 2 non-zero entries (240 of 512).  The H-point
+// transform is a Stockham autosort FFT with H / 64 values per lane: three
+// radix-8 passes at H = 512, four radix-4 passes at H = 256, exchanged through
+// a padded per-wave LDS buffer; a lane's twiddles do not depend on the frame
+// and stay in registers.  The first pass reads the staged samples directly
+// (its upper inputs are the zero padding: constants to the compiler).
+//
+// Band product: the 25 filter rows have 7 to 29 non-zero entries (357 of
+// 12,800); a band is summed over its support by two lanes, half each.
+//
+// What is uniform over a frame's wave in fp64 (the logarithm of segSNR, the
+// divisions) waits in LDS and runs once per chunk, one frame per lane.
+//
+// The clean side (cse_segsnr_prepare) runs the same frame code in fp64 and
+// leaves per frame a 224-byte record: ce[25], Wt[25], sum Wt, the silent flag
+// (f32) and s (f64).  The cell kernel never transforms x.
+#include "cse_common.hpp"
+
+#include "../../include/cse_segsnr.h"
+
+namespace cse {
+namespace seg {
+
+constexpr int NB = 25;        // critical bands
+constexpr int FW = 32;        // room per filter row (widest support: 29)
+constexpr int FWP = FW + 1;   // row stride of the LDS copy: the lanes of a band product read
+                              // one row each, and a stride of 32 words is two banks for all
+constexpr int REC = 56;       // f32 words per frame record
+constexpr int R_SUMW = 50, R_SILENT = 51, R_S = 52;
+constexpr int NT = 512;       // cell kernel: threads per workgroup
+constexpr int NW = NT / 64;
+constexpr int FCH = 16;       // frames per staged chunk
+constexpr int PNT = 256;      // clean-side kernel: threads per workgroup
+constexpr int PNW = PNT / 64;
+constexpr double EPS = 2.220446049250313e-16;  // 2^-52
+constexpr double LO = -10.0, HI = 35.0;
+
+struct Bands {  // support of each filter row: [lo, lo + n)
+    int lo[NB];
+    int n[NB];
+};
+
+template <int H>
+struct Cfg {
+    static constexpr int W = H / 16 * 15;        // 480 / 240
+    static constexpr int HOP = W / 4;
+    static constexpr int R = H == 512 ? 8 : 4;   // radix; also the values per lane (H / 64)
+    static constexpr int P = H == 512 ? 3 : 4;   // passes
+    static constexpr int NIN = (W / 2 + 63) / 64;  // non-zero inputs per lane in pass 0
+    static constexpr int BUF = H + H / 8;        // padded complex entries per wave
+    static constexpr int SPAN = (FCH - 1) * HOP + W;
+    static constexpr int CARRY = W - HOP;
+    static_assert(H == 512 || H == 256, "H is 512 (16 kHz) or 256 (8 kHz)");
+    static_assert(CARRY <= NT, "one carried sample per thread");
+};
+
+template <typename T>
+struct cx {
+    T x, y;
+};
+template <typename T>
+__device__ __forceinline__ cx<T> operator+(cx<T> a, cx<T> b) { return {a.x + b.x, a.y + b.y}; }
+template <typename T>
+__device__ __forceinline__ cx<T> operator-(cx<T> a, cx<T> b) { return {a.x - b.x, a.y - b.y}; }
+template <typename T>
+__device__ __forceinline__ cx<T> operator*(cx<T> a, cx<T> b) {
+    return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
+}
+template <typename T>
+__device__ __forceinline__ cx<T> mul_mi(cx<T> a) { return {a.y, -a.x}; }  // -i a
+
+// forward DFT (e^{-2 pi i nk/R}) in registers, natural order in and out
+template <typename T>
+__device__ __forceinline__ void dft4(cx<T>& a0, cx<T>& a1, cx<T>& a2, cx<T>& a3) {
+    const cx<T> b0 = a0 + a2, b2 = a0 - a2, b1 = a1 + a3, b3 = mul_mi(a1 - a3);
+    a0 = b0 + b1;
+    a2 = b0 - b1;
+    a1 = b2 + b3;
+    a3 = b2 - b3;
+}
+
+template <typename T>
+__device__ __forceinline__ void dft(cx<T> (&v)[4]) { dft4(v[0], v[1], v[2], v[3]); }
+
+template <typename T>
+__device__ __forceinline__ void dft(cx<T> (&v)[8]) {
+    constexpr T r2 = (T)0.70710678118654752440;
+    // even outputs: DFT4 of v[n] + v[n+4]; odd: DFT4 of W8^n (v[n] - v[n+4])
+    cx<T> e0 = v[0] + v[4], e1 = v[1] + v[5], e2 = v[2] + v[6], e3 = v[3] + v[7];
+    cx<T> d0 = v[0] - v[4], c1 = v[1] - v[5], d2 = mul_mi(v[2] - v[6]), c3 = v[3] - v[7];
+    cx<T> d1 = {r2 * (c1.x + c1.y), r2 * (c1.y - c1.x)};    // c1 (1 - i) / sqrt 2
+    cx<T> d3 = {r2 * (c3.y - c3.x), -r2 * (c3.x + c3.y)};   // c3 (-1 - i) / sqrt 2
+    dft4(e0, e1, e2, e3);
+    dft4(d0, d1, d2, d3);
+    v[0] = e0;
+    v[2] = e1;
+    v[4] = e2;
+    v[6] = e3;
+    v[1] = d0;
+    v[3] = d1;
+    v[5] = d2;
+    v[7] = d3;
+}
+
+// ordering of LDS accesses among the lanes of one wave (the LDS executes a
+// wave's DS instructions in issue order: a compiler-level barrier suffices)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Sum over the 64 lanes of a wave, all active; every lane gets the result.
+// Within a row of 16 lanes by DPP (quad swaps, then the half-row and row
+// mirrors), the four row sums by v_readlane: no LDS traffic, where
+// __shfl_xor costs two ds_bpermute per step for a double.
+template <int CTRL>
+__device__ __forceinline__ double dpp_add(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+    return v + __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double row_sum_of(double v, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
+                            __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+    v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+    v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+    v = dpp_add<0x141>(v);  // row_half_mirror
+    v = dpp_add<0x140>(v);  // row_mirror
+    return (row_sum_of(v, 0) + row_sum_of(v, 16)) + (row_sum_of(v, 32) + row_sum_of(v, 48));
+}
+
+__device__ __forceinline__ int pad(int i) { return i + (i >> 3); }
+
+// the per-lane constants of the transform: the twiddles of passes 1.. and of
+// the real-FFT split for the lane's bins k = lane + 64 r
+template <typename T, int H>
+struct Twiddles {
+    using C = Cfg<H>;
+    cx<T> tw[C::P - 1][C::R - 1];
+    cx<T> st0;  // e^{-2 pi i lane / NFFT}; bin lane + 64 r takes st0 e^{-pi i 64 r / H}
+    __device__ __forceinline__ void init(int lane) {
+        int ns = C::R;
+#pragma unroll
+        for (int p = 1; p < C::P; ++p) {
+            const int k = lane % ns;
+#pragma unroll
+            for (int r = 1; r < C::R; ++r) {
+                double s, c;
+                sincospi(-2.0 * (double)(k * r) / (double)(ns * C::R), &s, &c);
+                tw[p - 1][r - 1] = {(T)c, (T)s};
+            }
+            ns *= C::R;
+        }
+        double s, c;
+        sincospi(-(double)lane / (double)H, &s, &c);
+        st0 = {(T)c, (T)s};
+    }
+    // e^{-pi i 64 r / H}: sixteenths of a half turn, two per step at H = 256
+    static __device__ __forceinline__ cx<T> step(int r) {
+        constexpr T c1 = (T)0.92387953251128675613, s1 = (T)0.38268343236508977173;
+        constexpr T r2 = (T)0.70710678118654752440;
+        switch (r * (512 / H)) {
+            case 0: return {(T)1, (T)0};
+            case 1: return {c1, -s1};
+            case 2: return {r2, -r2};
+            case 3: return {s1, -c1};
+            case 4: return {(T)0, (T)-1};
+            case 5: return {-s1, -c1};
+            case 6: return {-r2, -r2};
+            default: return {-c1, -s1};  // 7
+        }
+    }
+};
+
+// H-point forward transform of one wave: v = the inputs z[lane + 64 r] of pass
+// 0; the result is left in buf (padded index), natural order.
+template <typename T, int H>
+__device__ __forceinline__ void wave_fft(cx<T>* buf, cx<T> (&v)[Cfg<H>::R],
+                                         const Twiddles<T, H>& tw, int lane) {
+    using C = Cfg<H>;
+    dft(v);
+#pragma unroll
+    for (int r = 0; r < C::R; ++r) buf[pad(lane * C::R + r)] = v[r];
+    wave_sync();
+    int ns = C::R;
+#pragma unroll
+    for (int p = 1; p < C::P; ++p) {
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) v[r] = buf[pad(lane + 64 * r)];
+        wave_sync();
+#pragma unroll
+        for (int r = 1; r < C::R; ++r) v[r] = v[r] * tw.tw[p - 1][r - 1];
+        dft(v);
+        const int j0 = (lane / ns) * ns * C::R + lane % ns;
+#pragma unroll
+        for (int r = 0; r < C::R; ++r) buf[pad(j0 + r * ns)] = v[r];
+        wave_sync();
+        ns *= C::R;
+    }
+}
+
+// |FFT_NFFT(f)[k]| for the lane's bins k = lane + 64 r from the H-point
+// transform in buf (the real-FFT split); the magnitudes then replace buf's
+// head as a plain T[H] array.  Returns the lane's share of their sum.
+template <typename T, int H>
+__device__ __forceinline__ T wave_magnitudes(cx<T>* buf, const Twiddles<T, H>& tw, int lane) {
+    using C = Cfg<H>;
+    T mag[C::R];
+    T sum = (T)0;
+#pragma unroll
+    for (int r = 0; r < C::R; ++r) {
+        const int k = lane + 64 * r;
+        const cx<T> a = buf[pad(k)];
+        cx<T> b = buf[pad((H - k) & (H - 1))];
+        b.y = -b.y;
+        const cx<T> e = a + b, d = mul_mi(a - b);       // 2 E[k], 2 O[k]
+        const cx<T> f = e + tw.st0 * (Twiddles<T, H>::step(r) * d);
+        mag[r] = (T)0.5 * sqrt(f.x * f.x + f.y * f.y);
+        sum += mag[r];
+    }
+    wave_sync();
+    T* m = (T*)buf;
+#pragma unroll
+    for (int r = 0; r < C::R; ++r) m[lane + 64 * r] = mag[r];
+    wave_sync();
+    return sum;
+}
+
+// the band's filter row times the magnitudes: lanes l and l + 32 sum half of
+// the support of band l each (l < 25); both end up with the whole sum
+template <typename T>
+__device__ __forceinline__ T wave_band(const T* m, const T* fv, const int* flo, const int* fn,
+                                       int lane) {
+    const int band = lane & 31, half = lane >> 5;
+    T acc = (T)0;
+    if (band < NB) {
+        const int n = fn[band], lo = flo[band], mid = (n + 1) >> 1;
+        const int t0 = half ? mid : 0, t1 = half ? n : mid;
+        for (int t = t0; t < t1; ++t) acc += fv[band * FWP + t] * m[lo + t];
+    }
+    acc += __shfl_xor(acc, 32, 64);
+    return acc;
+}
+
+// F[i][k] of the header, before the floor (fp64, numpy's operation order)
+__host__ __device__ inline double filter_entry(int i, int k, int H) {
+    const double cent[NB] = {50.0,    120.0,   190.0,   260.0,   330.0,   400.0,   470.0,
+                             540.0,   617.372, 703.378, 798.717, 904.128, 1020.38, 1148.30,
+                             1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71,
+                             2701.97, 2978.04, 3276.17, 3597.63};
+    const double band[NB] = {70.0,    70.0,    70.0,    70.0,    70.0,    70.0,    70.0,
+                             77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423,
+                             153.823, 168.154, 183.457, 199.776, 217.153, 235.631, 255.255,
+                             276.072, 298.126, 321.465, 346.136};
+    // cent / (sr/2) H with H / (sr/2) = 512 / 8000 = 256 / 4000 at both rates
+    const double nyq = H == 512 ? 8000.0 : 4000.0;
+    const double f0 = floor(cent[i] / nyq * (double)H);
+    const double bw = band[i] / nyq * (double)H;
+    const double q = ((double)k - f0) / bw;
+    return exp(-11.0 * (q * q) + log(band[0]) - log(band[i]));
+}
+
+// ---------------------------------------------------------------------------
+// clean side
+// ---------------------------------------------------------------------------
+struct Layout {
+    int64_t J;
+    int64_t filt, ja, x32, rec, total;  // byte offsets
+};
+
+static inline int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+
+static Layout layout(int64_t n_sig, int64_t len, int H) {
+    const int hop = H / 16 * 15 / 4;
+    Layout L;
+    L.J = len / hop - 4;
+    if (L.J < 0) L.J = 0;
+    L.filt = 0;  // int lo[32], int n[32], float vals[NB][FW]
+    L.ja = up256(64 * 4 + NB * FW * 4);
+    L.x32 = L.ja + up256(n_sig * 4);
+    L.rec = L.x32 + up256(n_sig * len * 4);
+    L.total = L.rec + up256(n_sig * L.J * REC * 4);
+    return L;
+}
+
+__global__ void __launch_bounds__(1024) segsnr_filter_kernel(Bands b, int H, int* flo, int* fn,
+                                                             float* fv) {
+    const int t = threadIdx.x;
+    if (t < 32) {
+        flo[t] = t < NB ? b.lo[t] : 0;
+        fn[t] = t < NB ? b.n[t] : 0;
+    }
+    for (int e = t; e < NB * FW; e += 1024) {
+        const int i = e / FW, c = e % FW;
+        fv[e] = c < b.n[i] ? (float)filter_entry(i, b.lo[i] + c, H) : 0.0f;
+    }
+}
+
+__global__ void __launch_bounds__(256) segsnr_x32_kernel(const double* __restrict__ x, int64_t n,
+                                                         float* __restrict__ x32) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) x32[i] = (float)x[i];
+}
+
+template <int H>
+__global__ void __launch_bounds__(PNT) segsnr_clean_kernel(const double* __restrict__ x,
+                                                           int64_t len, int64_t J, Bands bands,
+                                                           float* __restrict__ rec) {
+    using C = Cfg<H>;
+    __shared__ cx<double> buf[PNW][C::BUF];
+    __shared__ double wnd[C::W];
+    __shared__ double fv[NB * FWP];
+    __shared__ int flo[32], fn[32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < C::W; i += PNT) {
+        double s, c;
+        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
+        wnd[i] = 0.5 * (1.0 - c);
+    }
+    if (tid < 32) {
+        flo[tid] = tid < NB ? bands.lo[tid] : 0;
+        fn[tid] = tid < NB ? bands.n[tid] : 0;
+    }
+    for (int e = tid; e < NB * FW; e += PNT) {
+        const int i = e / FW, c = e % FW;
+        fv[i * FWP + c] = c < bands.n[i] ? filter_entry(i, bands.lo[i] + c, H) : 0.0;
+    }
+    __syncthreads();
+    const int64_t f = (int64_t)blockIdx.x * PNW + wave;
+    if (f >= J) return;  // wave-uniform; no workgroup barrier below
+    const int64_t sig = blockIdx.y;
+    const double* xs = x + sig * len + f * C::HOP;
+    float* r = rec + (sig * J + f) * REC;
+    Twiddles<double, H> tw;
+    tw.init(lane);
+    cx<double> v[C::R];
+    double sacc = 0.0;
+    bool nz = false;
+#pragma unroll
+    for (int q = 0; q < C::R; ++q) {
+        v[q] = {0.0, 0.0};
+        if (q < C::NIN) {
+            const int n = lane + 64 * q;
+            if (n < C::W / 2) {
+                const double a = xs[2 * n], b = xs[2 * n + 1];
+                nz = nz || a != 0.0 || b != 0.0;
+                v[q] = {a * wnd[2 * n], b * wnd[2 * n + 1]};
+                sacc += v[q].x * v[q].x + v[q].y * v[q].y;
+            }
+        }
+    }
+    const bool silent = __ballot(nz) == 0;
+    if (silent) {
+        if (lane < REC) r[lane] = lane == R_SILENT ? 1.0f : 0.0f;
+        return;
+    }
+    const double s = wave_sum(sacc);
+    wave_fft<double, H>(buf[wave], v, tw, lane);
+    const double sum = wave_sum(wave_magnitudes<double, H>(buf[wave], tw, lane));
+    const double ce = wave_band<double>((const double*)buf[wave], fv, flo, fn, lane) / (sum + EPS);
+    const double wt = pow(ce, 0.2);
+    const double sumw = wave_sum(lane < NB ? wt : 0.0);
+    if (lane < NB) {
+        r[lane] = (float)ce;
+        r[NB + lane] = (float)wt;
+    }
+    if (lane == 0) {
+        r[R_SUMW] = (float)sumw;
+        r[R_SILENT] = 0.0f;
+        *(double*)(r + R_S) = s;
+    }
+}
+
+__global__ void __launch_bounds__(256) segsnr_count_kernel(const float* __restrict__ rec, int64_t J,
+                                                           int* __restrict__ ja) {
+    __shared__ int red[256];
+    const int64_t sig = blockIdx.x;
+    int n = 0;
+    for (int64_t f = threadIdx.x; f < J; f += 256)
+        n += rec[(sig * J + f) * REC + R_SILENT] == 0.0f ? 1 : 0;
+    red[threadIdx.x] = n;
+    __syncthreads();
+    for (int s = 128; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ja[sig] = red[0];
+}
+
+// ---------------------------------------------------------------------------
+// cells
+// ---------------------------------------------------------------------------
+struct CellArgs {
+    const float* y;
+    const int64_t* y_offset;
+    const int32_t* lag;
+    const int32_t* sig_of;
+    int64_t len, J;
+    int clip;
+    const int* flo;
+    const int* fn;
+    const float* fv;
+    const int* ja;
+    const float* x32;
+    const float* rec;
+    double* seg;
+    double* fw;
+};
+
+// sample n of a cell's test signal: y shifted by the alignment lag, zero
+// outside [0, len), clipped (cse_stoi.hip's cell_sample)
+__device__ __forceinline__ float cell_sample(const float* y, int64_t n, int64_t len, int lag,
+                                             bool clip) {
+    const int64_t s = n - lag;
+    if (n < 0 || n >= len || s < 0 || s >= len) return 0.0f;
+    float v = y[s];
+    if (clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
+    return v;
+}
+
+template <int H>
+__global__ void __launch_bounds__(NT, 4) segsnr_cells_kernel(CellArgs a) {
+    using C = Cfg<H>;
+    __shared__ cx<float> buf[NW][C::BUF];
+    __shared__ __attribute__((aligned(8))) float sy[C::SPAN];
+    __shared__ __attribute__((aligned(8))) float sx[C::SPAN];
+    __shared__ __attribute__((aligned(8))) float wnd[C::W];
+    __shared__ float fv[NB * FWP];
+    __shared__ int flo[32], fn[32];
+    // per frame of the chunk: e (-1: silent frame) and the weighted band sum.
+    // The fp64 logarithm and divisions of a frame are uniform over its wave;
+    // they run once per chunk instead, one frame per lane of wave 0
+    __shared__ double fe[FCH], fnum[FCH];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t cell = blockIdx.x;
+    const int64_t sig = a.sig_of[cell];
+    const int lag = a.lag ? a.lag[cell] : 0;
+    const float* yc = a.y + a.y_offset[cell];
+    const float* xc = a.x32 + sig * a.len;
+    const bool clip = a.clip != 0, want_fw = a.fw != nullptr;
+    for (int i = tid; i < C::W; i += NT) {
+        double s, c;
+        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
+        wnd[i] = (float)(0.5 * (1.0 - c));
+    }
+    if (tid < 32) {
+        flo[tid] = a.flo[tid];
+        fn[tid] = a.fn[tid];
+    }
+    for (int e = tid; e < NB * FW; e += NT) fv[e / FW * FWP + e % FW] = a.fv[e];
+    Twiddles<float, H> tw;
+    tw.init(lane);
+    double seg_acc = 0.0, fw_acc = 0.0;  // thread t < FCH: the sums of frames t, t + FCH, ...
+    for (int64_t f0 = 0; f0 < a.J; f0 += FCH) {
+        const int nf = (int)((a.J - f0) < FCH ? (a.J - f0) : FCH);
+        const int span = (nf - 1) * C::HOP + C::W;
+        const int64_t base = f0 * C::HOP;
+        int start = 0;
+        if (f0 > 0) {  // the previous chunk was a full one: keep its last W - hop samples
+            float cy = 0.0f, cxv = 0.0f;
+            if (tid < C::CARRY) {
+                cy = sy[FCH * C::HOP + tid];
+                cxv = sx[FCH * C::HOP + tid];
+            }
+            __syncthreads();
+            if (tid < C::CARRY) {
+                sy[tid] = cy;
+                sx[tid] = cxv;
+            }
+            start = C::CARRY;
+        }
+        for (int i = start + tid; i < span; i += NT) {
+            sy[i] = cell_sample(yc, base + i, a.len, lag, clip);
+            sx[i] = xc[base + i];
+        }
+        __syncthreads();
+        for (int fr = wave; fr < nf; fr += NW) {
+            const float* r = a.rec + (sig * a.J + f0 + fr) * REC;
+            if (r[R_SILENT] != 0.0f) {  // wave-uniform
+                if (lane == 0) fe[fr] = -1.0;
+                continue;
+            }
+            const int fs = fr * C::HOP;
+            cx<float> v[C::R];
+            double eacc = 0.0;
+#pragma unroll
+            for (int q = 0; q < C::R; ++q) {
+                v[q] = {0.0f, 0.0f};
+                if (q < C::NIN) {
+                    const int n = lane + 64 * q;
+                    if (n < C::W / 2) {
+                        const float2 yy = *(const float2*)&sy[fs + 2 * n];
+                        const float2 xx = *(const float2*)&sx[fs + 2 * n];
+                        const float2 ww = *(const float2*)&wnd[2 * n];
+                        v[q] = {yy.x * ww.x, yy.y * ww.y};
+                        // (x - y) w: one rounding of the difference, not two of the
+                        // products it would cancel (frames near the 35 dB clamp)
+                        const float d0 = (xx.x - yy.x) * ww.x, d1 = (xx.y - yy.y) * ww.y;
+                        eacc += (double)(d0 * d0) + (double)(d1 * d1);
+                    }
+                }
+            }
+            const double e = wave_sum(eacc);
+            if (lane == 0) fe[fr] = e;
+            if (!want_fw) continue;
+            wave_fft<float, H>(buf[wave], v, tw, lane);
+            const double sum = wave_sum((double)wave_magnitudes<float, H>(buf[wave], tw, lane));
+            const float acc = wave_band<float>((const float*)buf[wave], fv, flo, fn, lane);
+            double num = 0.0;
+            if (lane < NB) {
+                const float pe = acc / (float)(sum + EPS);
+                const float ce = r[lane], wt = r[NB + lane];
+                const float dd = ce - pe;
+                const float err = fmaxf(dd * dd, (float)EPS);
+                const float snr = ce > 0.0f ? 10.0f * log10f(ce * ce / err) : 0.0f;
+                num = (double)(wt * snr);
+            }
+            num = wave_sum(num);
+            if (lane == 0) fnum[fr] = num;
+            wave_sync();  // the magnitudes are read before the next frame's pass 0 writes
+        }
+        __syncthreads();
+        // the frame values of the chunk (read before the next chunk's barrier,
+        // written after it)
+        if (tid < nf) {
+            const double e = fe[tid];
+            if (e >= 0.0) {
+                const float* r = a.rec + (sig * a.J + f0 + tid) * REC;
+                const double s = *(const double*)(r + R_S);
+                const double sv = 10.0 * log10(s / (e + EPS) + EPS);
+                seg_acc += fmin(fmax(sv, LO), HI);
+                if (want_fw) {
+                    const double fv_ = fnum[tid] / ((double)r[R_SUMW] + EPS);
+                    fw_acc += fmin(fmax(fv_, LO), HI);
+                }
+            }
+        }
+    }
+    if (wave != 0) return;  // no workgroup barrier below
+    const double s0 = wave_sum(seg_acc), s1 = wave_sum(fw_acc);
+    if (tid == 0) {
+        const int ja = a.ja[sig];
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        if (a.seg) a.seg[cell] = ja > 0 ? s0 / (double)ja : nan;
+        if (a.fw) a.fw[cell] = ja > 0 ? s1 / (double)ja : nan;
+    }
+}
+
+static int half_bins(int sr) { return sr == 16000 ? 512 : (sr == 8000 ? 256 : 0); }
+
+// the supports of the filter rows (the entries above the floor), on the host
+static bool band_supports(int H, Bands* b) {
+    const double floor_v = exp(-30.0 / (2.0 * 2.303));
+    for (int i = 0; i < NB; ++i) {
+        int lo = -1, hi = -1;
+        for (int k = 0; k < H; ++k)
+            if (filter_entry(i, k, H) > floor_v) {
+                if (lo < 0) lo = k;
+                hi = k;
+            }
+        if (lo < 0 || hi - lo + 1 > FW) return false;
+        b->lo[i] = lo;
+        b->n[i] = hi - lo + 1;  // lo + n <= H by construction
+    }
+    return true;
+}
+
+}  // namespace seg
+}  // namespace cse
+
+using namespace cse;
+
+extern "C" int64_t cse_segsnr_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
+    const int H = seg::half_bins(sr);
+    if (!H || n_sig < 0 || len < 0) return -1;
+    return seg::layout(n_sig, len, H).total;
+}
+
+extern "C" int64_t cse_segsnr_scratch_bytes(int64_t n_cells, int64_t len, int sr) {
+    if (!seg::half_bins(sr) || n_cells < 0 || len < 0) return -1;
+    return 0;  // the cell kernel keeps its intermediates in LDS and registers
+}
+
+extern "C" int cse_segsnr_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
+                                  void* workspace, cse_stream_t stream) {
+    const int H = seg::half_bins(sr);
+    CSE_CHECK_ARG(H != 0, "cse_segsnr_prepare: sr=%d not supported (16000, 8000)", sr);
+    CSE_CHECK_ARG(clean && workspace, "cse_segsnr_prepare: NULL argument");
+    CSE_CHECK_ARG(n_sig >= 1 && n_sig <= 65535 && len >= 1 && len < ((int64_t)1 << 36),
+                  "cse_segsnr_prepare: n_sig=%lld (1-65535) len=%lld", (long long)n_sig,
+                  (long long)len);
+    seg::Bands bands;
+    CSE_CHECK_ARG(seg::band_supports(H, &bands), "cse_segsnr_prepare: filter support too wide");
+    const seg::Layout L = seg::layout(n_sig, len, H);
+    unsigned char* ws = (unsigned char*)workspace;
+    int* flo = (int*)(ws + L.filt);
+    int* fn = flo + 32;
+    float* fv = (float*)(fn + 32);
+    int* ja = (int*)(ws + L.ja);
+    float* x32 = (float*)(ws + L.x32);
+    float* rec = (float*)(ws + L.rec);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = n_sig * len;
+    CSE_CHECK_ARG((n + 255) / 256 <= 0x7fffffffLL, "cse_segsnr_prepare: n_sig * len too large");
+    hipLaunchKernelGGL(seg::segsnr_filter_kernel, dim3(1), dim3(1024), 0, st, bands, H, flo, fn, fv);
+    hipLaunchKernelGGL(seg::segsnr_x32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       clean, n, x32);
+    if (L.J > 0) {
+        const dim3 grid((unsigned)((L.J + seg::PNW - 1) / seg::PNW), (unsigned)n_sig);
+        if (H == 512)
+            hipLaunchKernelGGL(seg::segsnr_clean_kernel<512>, grid, dim3(seg::PNT), 0, st, clean,
+                               len, L.J, bands, rec);
+        else
+            hipLaunchKernelGGL(seg::segsnr_clean_kernel<256>, grid, dim3(seg::PNT), 0, st, clean,
+                               len, L.J, bands, rec);
+    }
+    hipLaunchKernelGGL(seg::segsnr_count_kernel, dim3((unsigned)n_sig), dim3(256), 0, st,
+                       (const float*)rec, L.J, ja);
+    CSE_CHECK_LAUNCH("cse_segsnr_prepare");
+    return CSE_OK;
+}
+
+extern "C" int cse_segsnr_cells(const float* y, const int64_t* y_offset, const int32_t* lag,
+                                const int32_t* sig_of, int64_t n_cells, int64_t n_sig, int64_t len,
+                                int sr, int clip, const void* workspace, void* scratch,
+                                double* segsnr, double* fwsegsnr, cse_stream_t stream) {
+    (void)scratch;
+    const int H = seg::half_bins(sr);
+    CSE_CHECK_ARG(H != 0, "cse_segsnr_cells: sr=%d not supported (16000, 8000)", sr);
+    CSE_CHECK_ARG(y && y_offset && sig_of && workspace && (segsnr || fwsegsnr),
+                  "cse_segsnr_cells: NULL argument");
+    CSE_CHECK_ARG(n_cells >= 0 && n_cells <= 0x7fffffffLL && n_sig >= 1 && n_sig <= 65535 &&
+                      len >= 1 && len < ((int64_t)1 << 36),
+                  "cse_segsnr_cells: n_cells=%lld n_sig=%lld len=%lld", (long long)n_cells,
+                  (long long)n_sig, (long long)len);
+    if (n_cells == 0) return CSE_OK;
+    const seg::Layout L = seg::layout(n_sig, len, H);
+    const unsigned char* ws = (const unsigned char*)workspace;
+    seg::CellArgs a;
+    a.y = y;
+    a.y_offset = y_offset;
+    a.lag = lag;
+    a.sig_of = sig_of;
+    a.len = len;
+    a.J = L.J;
+    a.clip = clip;
+    a.flo = (const int*)(ws + L.filt);
+    a.fn = a.flo + 32;
+    a.fv = (const float*)(a.fn + 32);
+    a.ja = (const int*)(ws + L.ja);
+    a.x32 = (const float*)(ws + L.x32);
+    a.rec = (const float*)(ws + L.rec);
+    a.seg = segsnr;
+    a.fw = fwsegsnr;
+    hipStream_t st = (hipStream_t)stream;
+    if (H == 512)
+        hipLaunchKernelGGL(seg::segsnr_cells_kernel<512>, dim3((unsigned)n_cells), dim3(seg::NT), 0,
+                           st, a);
+    else
+        hipLaunchKernelGGL(seg::segsnr_cells_kernel<256>, dim3((unsigned)n_cells), dim3(seg::NT), 0,
+                           st, a);
+    CSE_CHECK_LAUNCH("cse_segsnr_cells");
+    return CSE_OK;
+}

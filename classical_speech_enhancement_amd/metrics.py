@@ -25,6 +25,13 @@ cse_estoi_cells: the same clean side plus per-(segment, frame) column
 statistics, the same resampling, silent-frame removal and band envelopes, then
 the row- and column-normalised correlation defined in include/cse_estoi.h
 (no jitter; norm + eps divisors).
+
+SegSnrPlan scores the two quality measures of include/cse_segsnr.h, segmental
+SNR and frequency-weighted segmental SNR (Hu & Loizou 2008's best non-PESQ
+predictor of quality for this project's algorithm families), the same way: the
+clean side once per batch (cse_segsnr_prepare), then any number of cells
+(cse_segsnr_cells) with STOI's lag / clip test-signal definition.  The
+reference scores neither; evaluate_audio_quality adds them only on request.
 """
 
 import math
@@ -158,6 +165,170 @@ class StoiPlan:
         return self.score_async(y, y_offset, sig_of, lag, clip).cpu().numpy()
 
 
+SEGSNR_RATES = (16000, 8000)
+# bound on the scratch of one cse_segsnr_cells launch: the cells per launch come
+# from this budget and the library's per-cell figure, never from a fixed count
+SEGSNR_SCRATCH_BYTES = 1 << 30
+# cells per launch when the kernel needs no scratch (the grid's x dimension)
+SEGSNR_MAX_CELLS = 1 << 20
+
+
+class SegSnrPlan:
+    """Clean side of segSNR / fwSegSNR for S equal-length signals (clean:
+    [S, L] f64 cuda) at 16 or 8 kHz."""
+
+    def __init__(self, clean, sr=STOI_SR):
+        if not _gpu_visible():
+            raise _lib.CseError("no GPU visible: the HIP engine has no CPU fallback")
+        self.lib = _lib.load()
+        clean = clean.contiguous()
+        if clean.dtype != torch.float64 or clean.dim() != 2 or not clean.is_cuda:
+            raise ValueError("clean must be a [S, L] float64 cuda tensor")
+        self.S, self.L = clean.shape
+        self.clean = clean
+        self.sr = int(sr)
+        nbytes = int(self.lib.cse_segsnr_workspace_bytes(self.S, self.L, self.sr))
+        if nbytes < 0:
+            raise NotImplementedError(f"segSNR: sample rate {sr} not supported (16000, 8000 Hz)")
+        self.ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=clean.device)
+        _lib.check(self.lib.cse_segsnr_prepare(_ptr(clean), self.S, self.L, self.sr, _ptr(self.ws),
+                                               _stream()), "cse_segsnr_prepare")
+        self._scratch = None
+
+    def cells_per_launch(self):
+        """Cells of one launch: SEGSNR_SCRATCH_BYTES over the library's scratch
+        per cell at this length and rate; SEGSNR_MAX_CELLS when it needs none."""
+        per = int(self.lib.cse_segsnr_scratch_bytes(1, self.L, self.sr))
+        if per <= 0:
+            return SEGSNR_MAX_CELLS
+        return int(max(1, min(SEGSNR_MAX_CELLS, SEGSNR_SCRATCH_BYTES // per)))
+
+    def _scratch_for(self, n):
+        nbytes = int(self.lib.cse_segsnr_scratch_bytes(n, self.L, self.sr))
+        if nbytes <= 0:
+            return None
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.clean.device)
+        return self._scratch
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True, out=None, which="both"):
+        """Enqueue both scores of every cell; returns the [n, 2] f64 cuda result
+        (segsnr, fwsegsnr).  The arguments are StoiPlan.score_async's: host
+        index arrays are validated and uploaded, cuda tensors (int64 / int32 /
+        int32) are taken as they are.  which="segsnr" / "fwsegsnr" computes
+        that score alone (the other column is NaN; "segsnr" skips the
+        transforms)."""
+        dev = self.clean.device
+        if which not in ("both", "segsnr", "fwsegsnr"):
+            raise ValueError(f"which={which!r}: 'both', 'segsnr' or 'fwsegsnr'")
+        if y.dtype != torch.float32 or not y.is_cuda:
+            raise ValueError("y must be a float32 cuda tensor")
+        if torch.is_tensor(y_offset):
+            off, sig = y_offset, sig_of
+            if not torch.is_tensor(sig):
+                raise ValueError("sig_of must be a cuda tensor when y_offset is one")
+            if off.dtype != torch.int64 or sig.dtype != torch.int32:
+                raise ValueError("device y_offset / sig_of must be int64 / int32")
+            if off.device != dev or sig.device != dev:
+                raise ValueError("device y_offset / sig_of must live on the clean signal's GPU")
+            if not (off.is_contiguous() and sig.is_contiguous()):
+                raise ValueError("device y_offset / sig_of must be contiguous")
+            n = int(off.numel())
+            if int(sig.numel()) != n:
+                raise ValueError("y_offset and sig_of differ in length")
+        else:
+            off_h = np.asarray(y_offset, dtype=np.int64)
+            sig_h = np.asarray(sig_of, dtype=np.int32)
+            n = len(off_h)
+            if len(sig_h) != n:
+                raise ValueError("y_offset and sig_of differ in length")
+            if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= self.S):
+                raise ValueError("sig_of out of range")
+            if n and (int(off_h.min()) < 0 or int(off_h.max()) + self.L > y.numel()):
+                raise ValueError("a cell's output runs past the end of y")
+            off = torch.as_tensor(off_h, device=dev)
+            sig = torch.as_tensor(sig_h, device=dev)
+        lg = None
+        if lag is not None:
+            if torch.is_tensor(lag):
+                if lag.device != dev:
+                    raise ValueError("device lag must live on the clean signal's GPU")
+                lg = lag.to(torch.int32).contiguous()
+            else:
+                lg = torch.as_tensor(np.asarray(lag, dtype=np.int32), device=dev)
+            if int(lg.numel()) != n:
+                raise ValueError("lag and y_offset differ in length")
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        if out.shape != (n, 2) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n, 2] float64 tensor")
+        # the library writes one column each: planar scratch rows, then one copy
+        cols = torch.full((2, n), float("nan"), dtype=torch.float64, device=dev)
+        step = self.cells_per_launch()
+        for s in range(0, n, step):
+            m = min(step, n - s)
+            scratch = self._scratch_for(m)
+            _lib.check(self.lib.cse_segsnr_cells(
+                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
+                self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
+                None if scratch is None else _ptr(scratch),
+                None if which == "fwsegsnr" else _ptr(cols[0, s:]),
+                None if which == "segsnr" else _ptr(cols[1, s:]), _stream()), "cse_segsnr_cells")
+        out.copy_(cols.t())
+        return out
+
+    def score(self, y, y_offset, sig_of, lag=None, clip=True, which="both"):
+        """score_async, synchronised: [n, 2] numpy (segsnr, fwsegsnr); NaN: no
+        frame, or no non-silent frame."""
+        return self.score_async(y, y_offset, sig_of, lag, clip, which=which).cpu().numpy()
+
+
+def _segsnr_pair(x, y, fs, which):
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.shape != y.shape:
+        raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
+    if x.ndim != 1 or x.size == 0:
+        raise ValueError("segsnr expects non-empty 1-D signals")
+    plan = SegSnrPlan(torch.as_tensor(x).cuda().view(1, -1), fs)
+    yd = torch.as_tensor(y.astype(np.float32)).cuda()
+    v = float(plan.score(yd, [0], [0], clip=False, which=which)[0, 0 if which == "segsnr" else 1])
+    if math.isnan(v):
+        raise ValueError("no non-silent 30-ms frame")
+    return v
+
+
+def segsnr(x, y, fs):
+    """Segmental SNR in dB (include/cse_segsnr.h) of y against the clean x."""
+    return _segsnr_pair(x, y, fs, "segsnr")
+
+
+def fwsegsnr(x, y, fs):
+    """Frequency-weighted segmental SNR in dB (include/cse_segsnr.h)."""
+    return _segsnr_pair(x, y, fs, "fwsegsnr")
+
+
+def _calculate_quality(fn, name, clean_reference, test_audio, sr):
+    try:
+        n = min(len(clean_reference), len(test_audio))
+        return fn(np.asarray(clean_reference)[:n], np.asarray(test_audio)[:n], sr)
+    except (NotImplementedError, _lib.CseError):
+        raise  # no device / unsupported: not a score failure
+    except Exception as e:  # calculate_stoi's catch-all
+        print(f"{name} calculation failed: {e}")
+        return None
+
+
+def calculate_segsnr(clean_reference, test_audio, sr):
+    """segsnr with calculate_stoi's shape: trim to the common length, None on failure."""
+    return _calculate_quality(segsnr, "segSNR", clean_reference, test_audio, sr)
+
+
+def calculate_fwsegsnr(clean_reference, test_audio, sr):
+    """fwsegsnr with calculate_stoi's shape: trim to the common length, None on failure."""
+    return _calculate_quality(fwsegsnr, "fwSegSNR", clean_reference, test_audio, sr)
+
+
 def stoi(x, y, fs_sig, extended=False):
     """pystoi ``stoi(x, y, fs_sig, extended=False)`` on the device; with
     extended=True, extended STOI as include/cse_estoi.h defines it."""
@@ -224,8 +395,10 @@ def calculate_combined_speech_score(stoi_score, pesq_score):
     return 0.5 * stoi_score + 0.5 * (max(0, pesq_score) / 4.5)
 
 
-def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name=""):
-    """evaluation_metrics.evaluate_audio_quality (:61-101), same keys."""
+def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name="",
+                           quality=False):
+    """evaluation_metrics.evaluate_audio_quality (:61-101), same keys;
+    quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement)."""
     results = {}
     s_noisy = calculate_stoi(clean_reference, noisy_audio, sr)
     s_enh = calculate_stoi(clean_reference, enhanced_audio, sr)
@@ -242,6 +415,14 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     snr_val = calculate_snr(clean_reference, enhanced_audio)
     if snr_val is not None:
         results["snr_enhanced"] = snr_val
+    if quality:
+        for key, fn in (("segsnr", calculate_segsnr), ("fwsegsnr", calculate_fwsegsnr)):
+            q_noisy = fn(clean_reference, noisy_audio, sr)
+            q_enh = fn(clean_reference, enhanced_audio, sr)
+            if q_noisy is not None and q_enh is not None:
+                results[f"{key}_noisy"] = q_noisy
+                results[f"{key}_enhanced"] = q_enh
+                results[f"{key}_improvement"] = q_enh - q_noisy
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:
@@ -249,4 +430,7 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
               f"(+{results['stoi_improvement']:.4f})")
     if "snr_enhanced" in results:
         print(f"SNR (Enhanced): {results['snr_enhanced']:.2f} dB")
+    for key, label in (("segsnr", "segSNR"), ("fwsegsnr", "fwSegSNR")):
+        if f"{key}_noisy" in results:
+            print(f"{label}: {results[key + '_noisy']:.2f} -> {results[key + '_enhanced']:.2f} dB")
     return results

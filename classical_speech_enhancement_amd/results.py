@@ -20,6 +20,12 @@ key keeps the reference's meaning.  The STOI-optimal cell fills the `*_stoiopt`
 STOI/SNR columns and `best_params_stoi`.  The SNR-optimal cell, which the
 reference does not select, is reported under keys of its own: snr_snropt and
 best_params_snr (and snr_snropt_mean in summary_means.json).
+
+A quality=True sweep (search.run_sweep) adds keys of its own in the same way:
+segsnr_noisy, fwsegsnr_noisy, and the fwSegSNR-optimal cell's fwsegsnr_best,
+best_params_fwsegsnr and snr_fwsegopt (their means in summary_means.json).  A
+row made without them has none of these keys, and the summary then has no such
+means.
 """
 
 import json
@@ -43,20 +49,41 @@ SUMMARY_KEYS = (("stoi_noisy_mean", "stoi_noisy"), ("pesq_noisy_mean", "pesq_noi
                 ("snr_balopt_mean", "snr_balopt"), ("snr_snropt_mean", "snr_snropt"))
 
 
+QUALITY_ARGS = ("segsnr_noisy", "fwsegsnr_noisy", "fwsegsnr_best", "fwsegsnr_params",
+                "snr_fwsegopt")
+QUALITY_KEYS = ("segsnr_noisy", "fwsegsnr_noisy", "fwsegsnr_best", "best_params_fwsegsnr",
+                "snr_fwsegopt")
+QUALITY_SUMMARY_KEYS = (("segsnr_noisy_mean", "segsnr_noisy"),
+                        ("fwsegsnr_noisy_mean", "fwsegsnr_noisy"),
+                        ("fwsegsnr_best_mean", "fwsegsnr_best"),
+                        ("snr_fwsegopt_mean", "snr_fwsegopt"))
+
+
 def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
-               stoi_best=None, stoi_params=None, snr_stoiopt=None):
+               stoi_best=None, stoi_params=None, snr_stoiopt=None, **quality):
     """One all_results.json row (run_algorithm_on_pair :314-338).  STOI
     fields come from the device STOI (the STOI-optimal cell fills
     stoi_stoiopt / snr_stoiopt / best_params_stoi); PESQ fields are None (no
     pesq extension), and so are the PESQ-opt and balance-opt columns
     (:320-333: the balance objective needs PESQ).  The SNR-optimal cell goes
-    to the extra keys snr_snropt / best_params_snr only."""
+    to the extra keys snr_snropt / best_params_snr only.  The quality keywords
+    (all or none: segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best, fwsegsnr_params,
+    snr_fwsegopt) add the QUALITY_KEYS of a quality=True sweep."""
     row = {k: None for k in ROW_KEYS}
     row.update(alg=alg, stem=stem, sr=int(sr), snr_noisy=snr_noisy,
                best_params_stoi=dict(stoi_params or {}), best_params_pesq={},
                best_params_balanced={}, snr_snropt=best_snr,
                best_params_snr=dict(best_params or {}),
                stoi_noisy=stoi_noisy, stoi_stoiopt=stoi_best, snr_stoiopt=snr_stoiopt)
+    if quality:
+        unknown = set(quality) - set(QUALITY_ARGS)
+        if unknown:
+            raise TypeError(f"result_row: unexpected keywords {sorted(unknown)}")
+        row.update(segsnr_noisy=quality.get("segsnr_noisy"),
+                   fwsegsnr_noisy=quality.get("fwsegsnr_noisy"),
+                   fwsegsnr_best=quality.get("fwsegsnr_best"),
+                   best_params_fwsegsnr=dict(quality.get("fwsegsnr_params") or {}),
+                   snr_fwsegopt=quality.get("snr_fwsegopt"))
     return row
 
 
@@ -76,6 +103,9 @@ def summary_means(all_results, algorithms):
         entry = {"count": len(rows)}
         for key, field in SUMMARY_KEYS:
             entry[key] = safe_mean([r.get(field) for r in rows])
+        if any("fwsegsnr_best" in r for r in rows):  # a quality=True sweep
+            for key, field in QUALITY_SUMMARY_KEYS:
+                entry[key] = safe_mean([r.get(field) for r in rows])
         out[alg] = entry
     return out
 

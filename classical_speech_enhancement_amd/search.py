@@ -38,6 +38,13 @@ extended=True (run_grid, optimize_parameters, run_sweep; stoi="extended" in
 engine_compute) scores extended STOI in place of STOI (cse_estoi_cells,
 include/cse_estoi.h): the STOI column and every stoi field then hold ESTOI, and
 the selection and its tolerance are the STOI objective's.
+
+quality=True (engine_compute, run_grid, optimize_parameters, run_sweep) adds the
+quality objective the reference takes from PESQ: segmental SNR and
+frequency-weighted segmental SNR (cse_segsnr_cells, include/cse_segsnr.h;
+Hu & Loizou 2008) of the same finalised waveforms, as two more table columns
+(QUALITY_COLUMNS) with objectives "segsnr" and "fwsegsnr".  The default leaves
+every table, record and result as it was.
 """
 
 import math
@@ -51,7 +58,9 @@ from .parameter_ranges import ALGORITHM_GRIDS, grid_cells
 # per-bin cost weights (measured kernel time per frame, OMLSA ~ 3x SS)
 ALGO_WEIGHT = {"spectralSubtractor": 1.0, "wiener": 1.1, "mmse": 2.0, "omlsa": 3.0}
 # tolerance of the best-so-far update per objective (speech_enhancement_comparison.py:183,194,205)
-TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5}
+# segsnr / fwsegsnr (dB): the reference's step for PESQ, the quality objective they stand in for
+TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5,
+             "segsnr": 1e-3, "fwsegsnr": 1e-3}
 
 # one float64 row per cell.  lag: finalize_enhanced's alignment lag (0 when
 # not aligned); xstatus: cse_xcorr_lag's status (engine: XCORR_OK, XCORR_FLAT =
@@ -60,6 +69,11 @@ RECORD_FIELDS = ("cell_id", "sse", "snr", "finite", "stoi", "lag", "xstatus")
 TABLE_COLUMN = {"sse": 0, "snr": 1, "finite": 2, "stoi": 3, "lag": 4,
                 "xstatus": 5}  # table = records without cell_id
 NCOL = len(RECORD_FIELDS) - 1
+# quality=True tables carry two more columns after the NCOL ones
+QUALITY_COLUMNS = {"segsnr": 6, "fwsegsnr": 7}
+# where select_best's scan starts: the reference's -1 (speech_enhancement_comparison.py:126-141)
+# unless the objective's values go below it (dB scores clamped to [-10, 35])
+SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf}
 # bound on the cell waveforms held at once for STOI scoring (f32 bytes): 48 GiB
 # of the 288 GB HBM, i.e. 10 full 10-s pairs (7,308 computed cells x 640 KB each)
 # per batch, two batches in flight.  100-pair sweep (late r04, call_r04s.sh in profiles/r04_commands.md):
@@ -270,11 +284,14 @@ def _unique_inverse(x):
     return np.flatnonzero(mark), rank[x]
 
 
-def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True):
+def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True, quality=False):
     """Device compute of the cells ``ids``: per-cell (sse, snr, finite, stoi,
     lag, xstatus), scored after finalize_enhanced's alignment (align=False: at
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
     waveforms are kept); stoi="extended" fills it with extended STOI.
+    quality=True appends segsnr and fwsegsnr (QUALITY_COLUMNS; NaN where the
+    cell is not finite), scored on the side stream from the same waveforms,
+    with or without STOI.
 
     clean/noisy: lists of 1-D float arrays (host) indexed by pair.  Pairs are
     batched by length (the engine's signal batches are rectangular), and, when
@@ -297,7 +314,7 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True)
     eng = engine or Engine()
     size0 = eng.plan_cache_size
     try:
-        return _engine_compute(eng, clean, noisy, specs, ids, align, stoi)
+        return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, bool(quality))
     finally:
         if own:
             eng._plan_cache.clear()
@@ -307,10 +324,11 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True)
                 eng._plan_cache.popitem(last=False)
 
 
-def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
+def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False):
     import torch
     from .engine import snr_db, spec_fingerprint, structure_digest
-    from .metrics import StoiPlan
+    from .metrics import SegSnrPlan, StoiPlan
+    keep = bool(stoi) or quality  # the cell waveforms are scored on the side stream
     ids = np.asarray(ids, dtype=np.int64)
     lengths = [len(x) for x in noisy]
     js_specs = isinstance(specs, JobSpecs)
@@ -320,7 +338,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
     else:
         comp, back = ids, np.arange(len(ids))
         pair_of = np.fromiter((specs[c][0] for c in comp), dtype=np.int64, count=len(comp))
-    vals = np.full((len(comp), NCOL), np.nan)
+    vals = np.full((len(comp), NCOL + (2 if quality else 0)), np.nan)
     by_len = OrderedDict()
     upairs, first = np.unique(pair_of, return_index=True)
     for pair in upairs[np.argsort(first, kind="stable")].tolist():  # first-appearance order
@@ -330,17 +348,21 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
     # (tools/overlap_probe.py: 20.4 -> 17.6 ms for one launch of each).
     # ready[key]: event after the last STOI that read the waveforms of the
     # plan with that reuse key (a reusing run overwrites them in place).
-    main = torch.cuda.current_stream() if stoi else None
-    side = eng.side_stream() if stoi else None
+    main = torch.cuda.current_stream() if keep else None
+    side = eng.side_stream() if keep else None
     inflight, ready = [], {}
-    if stoi:  # consecutive batches alternate between two plans (waveform buffers)
+    if keep:  # consecutive batches alternate between two plans (waveform buffers)
         eng.plan_cache_size = max(eng.plan_cache_size, 2)
     nbatch = 0
 
     def collect(item):
-        rows_, fin_, out_, ev_, _refs = item
+        rows_, fin_, out_, qout_, ev_, _refs = item
         ev_.synchronize()
-        vals[rows_, 3] = np.where(fin_, out_.cpu().numpy(), np.nan)
+        if out_ is not None:
+            vals[rows_, 3] = np.where(fin_, out_.cpu().numpy(), np.nan)
+        if qout_ is not None:
+            vals[rows_, NCOL:] = np.where(np.asarray(fin_, dtype=bool)[:, None],
+                                          qout_.cpu().numpy(), np.nan)
 
     sorted_pairs = len(pair_of) < 2 or bool((pair_of[1:] >= pair_of[:-1]).all())
     for L, pairs_l in by_len.items():
@@ -351,10 +373,10 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
         else:
             rows = {p: np.flatnonzero(pair_of == p) for p in pairs_l}
         batches, cur, n_cur = [], [], 0
-        cap = stoi_wave_bytes() if stoi else 0
+        cap = stoi_wave_bytes() if keep else 0
         for pair in pairs_l:
             n = len(rows[pair])
-            if stoi and cur and (n_cur + n) * L * 4 > cap:
+            if keep and cur and (n_cur + n) * L * 4 > cap:
                 batches.append(cur)
                 cur, n_cur = [], 0
             cur.append(pair)
@@ -370,10 +392,12 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
             cpow = np.array([float(np.dot(np.asarray(clean[p], np.float64),
                                           np.asarray(clean[p], np.float64))) for p in pairs])
             splan = StoiPlan(cl, extended=(stoi == "extended")) if stoi else None
+            qplan = SegSnrPlan(cl) if quality else None
             state = {}
 
-            def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, state=state):
-                """one n_fft's cells are final: queue their STOI on the side stream"""
+            def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, qplan=qplan,
+                        state=state):
+                """one n_fft's cells are final: queue their scores on the side stream"""
                 idx = np.asarray(p.idx, dtype=np.int64)
                 lg = lag if lag is not None else np.zeros(len(idx), dtype=np.int64)
                 # uploads on the main stream (a pageable copy would wait for the
@@ -383,12 +407,17 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
                 lag_d = torch.as_tensor(np.asarray(lg, dtype=np.int32)).cuda()
                 y = p.y_all.view(-1)  # the run's waveform buffer (every n_fft's rows)
                 side.wait_stream(main)
+                out = qout = None
                 with torch.cuda.stream(side):
-                    out = splan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
+                    if splan is not None:
+                        out = splan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
+                    if qplan is not None:
+                        qout = qplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 state["ev"] = ev
-                inflight.append((js[idx], fin, out, ev, (y, off_d, sig_d, lag_d, splan)))
+                inflight.append((js[idx], fin, out, qout, ev,
+                                 (y, off_d, sig_d, lag_d, splan, qplan)))
                 while len(inflight) > 2:  # bound the STOI scratch held in flight
                     collect(inflight.pop(0))
 
@@ -406,17 +435,17 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
                 run_specs = sub()
                 key = spec_fingerprint(run_specs)
                 run_kw = dict(reuse=key)
-            if stoi:  # the next batch's run overlaps this batch's STOI
+            if keep:  # the next batch's run overlaps this batch's STOI
                 key = (key, nbatch % 2)
                 run_kw["reuse"] = key
             nbatch += 1
             rkey = (L, len(pairs), key)
-            if stoi:
+            if keep:
                 if rkey in ready:  # the plan's waveforms are still read by that STOI
                     main.wait_event(ready[rkey])
                 run_kw["on_plan"] = on_plan
-            res = eng.run(nz, run_specs, clean=cl, align=align, want_waveforms=stoi, **run_kw)
-            if stoi:
+            res = eng.run(nz, run_specs, clean=cl, align=align, want_waveforms=keep, **run_kw)
+            if keep:
                 ready[rkey] = state["ev"]
             vals[js, 0] = res["sse"]
             vals[js, 1] = snr_db(res["sse"], cpow[sig])
@@ -433,9 +462,11 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi):
 
 
 def gather_records(local, n_total, group=None, device=None):
-    """All-gather per-cell records [n_local, 1 + NCOL] (RECORD_FIELDS) from
-    every rank into one [n_total, NCOL] table indexed by cell_id.  Fixed-size
-    rows padded to the largest shard so one all_gather_into_tensor moves them."""
+    """All-gather per-cell records [n_local, 1 + NCOL] (RECORD_FIELDS; 1 + NCOL + 2
+    with the quality columns) from every rank into one [n_total, width - 1]
+    table indexed by cell_id.  The width is the records' own (every rank's
+    alike).  Fixed-size rows padded to the largest shard so one
+    all_gather_into_tensor moves them."""
     import torch
     import torch.distributed as dist
     dist_on = group is not None or (dist.is_available() and dist.is_initialized())
@@ -444,8 +475,11 @@ def gather_records(local, n_total, group=None, device=None):
         if device is None and dist.get_backend(group) == "nccl":
             # RCCL moves device tensors only: gather on this rank's GPU
             device = torch.device("cuda", torch.cuda.current_device())
-    width = 1 + NCOL
-    rec = torch.as_tensor(np.asarray(local, dtype=np.float64).reshape(-1, width))
+    local = np.asarray(local, dtype=np.float64)
+    width = local.shape[1] if local.ndim == 2 else 1 + NCOL
+    if width < 1 + NCOL:
+        raise ValueError(f"gather: records of {width} columns (at least {1 + NCOL})")
+    rec = torch.as_tensor(local.reshape(-1, width))
     if dist_on:  # the collective runs at any world size, 1 included
         n = torch.tensor([rec.shape[0]], dtype=torch.int64, device=device)
         counts = torch.zeros(world, dtype=torch.int64, device=device)
@@ -469,22 +503,22 @@ def gather_records(local, n_total, group=None, device=None):
                            f"({len(ids) - int(np.count_nonzero(seen))} duplicates or out of range)")
     if np.array_equal(ids, np.arange(n_total)):
         return rec[:, 1:]  # already in cell order (a view: no copy of the table)
-    table = np.full((n_total, NCOL), np.nan)
+    table = np.full((n_total, width - 1), np.nan)
     table[ids] = rec[:, 1:]
     return table
 
 
-def _scan_records(sc, rec, ids, tol):
+def _scan_records(sc, rec, ids, tol, start=-1.0):
     """The sequential scan over the strict running maxima of one group (see
     select_best): returns (winner id or -1, score or None)."""
-    incumbent, win = -1.0, -1
+    incumbent, win = start, -1
     for k in rec.tolist():
         if sc[k] > incumbent + tol:
             incumbent, win = float(sc[k]), int(ids[k])
     return win, (incumbent if win >= 0 else None)
 
 
-def _select_best_blocks(specs, table, col, tol):
+def _select_best_blocks(specs, table, col, tol, start=-1.0):
     """select_best over a JobSpecs table: each algorithm's cells of all pairs
     as one [pairs, grid] block (the columns of a (pair, algorithm) run are
     contiguous), running maxima along the grid axis in one call."""
@@ -506,7 +540,8 @@ def _select_best_blocks(specs, table, col, tol):
             recs = sc > prev
             for pair in range(n_pairs):
                 ids = pair * specs.per_pair + off + np.arange(n)
-                found[(pair, a)] = _scan_records(sc[pair], np.flatnonzero(recs[pair]), ids, tol)
+                found[(pair, a)] = _scan_records(sc[pair], np.flatnonzero(recs[pair]), ids, tol,
+                                                 start)
         else:
             for pair in range(n_pairs):
                 found[(pair, a)] = (-1, None)
@@ -521,13 +556,25 @@ def select_best(specs, table, objective="snr", tol=None):
     Non-finite cells are skipped like finalize_enhanced returning None
     (speech_enhancement_comparison.py:102-103,173-175); the incumbent starts
     at -1 (:126-141); a NaN score (pystoi failure -> None) is skipped like
-    :182-183.  Returns {(pair, alg): (cell_id or -1, score)}."""
+    :182-183.  Returns {(pair, alg): (cell_id or -1, score)}.
+
+    "segsnr" / "fwsegsnr" (a quality=True table): the same scan with their
+    tolerance, started below every score (SCAN_START): the reference's -1 is a
+    floor for scores that are never negative, and these are dB values clamped
+    to [-10, 35], so the first scored cell is always taken."""
     tol = TOLERANCE[objective] if tol is None else tol
-    if objective not in ("snr", "stoi"):
+    if objective in QUALITY_COLUMNS:
+        col = QUALITY_COLUMNS[objective]
+        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
+            raise ValueError(f"objective {objective!r} needs a quality=True table of "
+                             f"{NCOL + 2} columns, this one has {np.shape(table)[-1]}")
+    elif objective in ("snr", "stoi"):
+        col = TABLE_COLUMN[objective]
+    else:
         raise ValueError(f"objective {objective!r} is not scored on the device (pesq is absent)")
-    col = TABLE_COLUMN[objective]
+    scan_start = SCAN_START.get(objective, -1.0)
     if isinstance(specs, JobSpecs) and tol >= 0.0:
-        return _select_best_blocks(specs, table, col, tol)
+        return _select_best_blocks(specs, table, col, tol, scan_start)
     groups = OrderedDict()
     if isinstance(specs, JobSpecs):  # (pair, algorithm) runs are contiguous
         per = [len(specs.cells[a]) for a in specs.algorithms]
@@ -545,7 +592,7 @@ def select_best(specs, table, objective="snr", tol=None):
         sc = table[ids, col]
         ok = (table[ids, 2] != 0) & (sc == sc)  # finite cell, score not NaN
         sc = np.where(ok, sc, -np.inf)
-        incumbent, win = -1.0, -1
+        incumbent, win = scan_start, -1
         if tol >= 0.0 and len(sc):
             # Only a strict running maximum can replace the incumbent: after
             # any cell j the incumbent is >= sc[j] - tol (it took sc[j], or
@@ -553,7 +600,7 @@ def select_best(specs, table, objective="snr", tol=None):
             # never clears incumbent + tol and leaves the state alone.  The
             # scan runs over those records only (a few per group).
             prev = np.maximum.accumulate(np.concatenate(([-np.inf], sc[:-1])))
-            best[key] = _scan_records(sc, np.flatnonzero(sc > prev), ids, tol)
+            best[key] = _scan_records(sc, np.flatnonzero(sc > prev), ids, tol, scan_start)
             continue
         else:
             start = 0  # negative tolerance: the plain jump scan
@@ -568,14 +615,16 @@ def select_best(specs, table, objective="snr", tol=None):
 
 
 def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
-             extended=False):
+             extended=False, quality=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
     gets the full table (all_gather); the selection is the deterministic
     sequential scan, identical on every rank.  extended=True: the default
     compute (engine_compute) scores extended STOI into the stoi column; a
-    compute function given by the caller scores what it scores."""
+    compute function given by the caller scores what it scores.  quality=True:
+    the table has NCOL + 2 columns (QUALITY_COLUMNS: segsnr, fwsegsnr), filled
+    by the default compute; a caller's compute function returns them itself."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
@@ -583,11 +632,16 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     lengths = [len(x) for x in noisy]
     rank_of, _ = assign_shards(specs, lengths, world)
     ids = np.nonzero(rank_of == rank)[0]
-    if compute is None and extended:
+    ncol = NCOL + (2 if quality else 0)
+    if compute is None and (extended or quality):
         def compute(clean, noisy, specs, ids):
-            return engine_compute(clean, noisy, specs, ids, stoi="extended")
+            return engine_compute(clean, noisy, specs, ids,
+                                  stoi="extended" if extended else True, quality=quality)
     compute = compute or engine_compute
-    vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, NCOL))
+    vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, ncol))
+    if np.ndim(vals) != 2 or np.shape(vals)[1] != ncol:
+        raise ValueError(f"compute returned rows of shape {np.shape(vals)}, expected "
+                         f"{ncol} columns (quality={bool(quality)})")
     if not dist_on and len(ids) == len(specs):  # one process, every cell in order: no gather
         table = np.asarray(vals, dtype=np.float64)
     else:
@@ -607,12 +661,19 @@ def _device_stoi(clean, test, sr, extended=False):
     return calculate_stoi(clean, test, sr, extended=extended)
 
 
+def _device_quality(clean, test, sr):
+    """(segsnr, fwsegsnr) of test against clean on the device, None for a failure."""
+    from .metrics import calculate_fwsegsnr, calculate_segsnr
+    return calculate_segsnr(clean, test, sr), calculate_fwsegsnr(clean, test, sr)
+
+
 def _opt(v):
     return None if v != v else float(v)
 
 
 def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_ranges=None,
-                        compute=None, stoi_fn=None, extended=False):
+                        compute=None, stoi_fn=None, extended=False, quality=False,
+                        quality_fn=None):
     """Single-pair, single-algorithm mirror of the reference's
     optimize_parameters (speech_enhancement_comparison.py:109-252), scored by
     STOI and SNR: returns {'stoi': {'score', 'params', 'cell', 'snr'},
@@ -622,7 +683,12 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     cell has a STOI value (a compute function that does not score STOI).
     extended=True: the cells and the baseline are scored with extended STOI
     (every 'stoi' value above is then ESTOI) and the result carries
-    'extended': True."""
+    'extended': True.
+    quality=True: the table has the two quality columns and the result gains
+    'segsnr' and 'fwsegsnr' entries shaped like 'stoi' ({'score', 'params',
+    'cell', 'snr'}, None when no cell has the score), with their baselines
+    (quality_fn(clean, noisy, sr) -> (segsnr, fwsegsnr); default: the device)
+    and improvements."""
     from .engine import canonical_algo
     if sr != 16000:
         raise ValueError("the device path runs at 16 kHz (prepare_pair resamples to 16 kHz)")
@@ -631,7 +697,8 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     specs = job_specs(1, [alg], grids)
     clean = [np.asarray(clean_reference, np.float64)]
     noisy = [np.asarray(noisy_audio, np.float64)]
-    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended)
+    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended,
+                           quality=quality)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -652,11 +719,24 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
                        "snr": float(table[sid, 1])}
         out["baseline"]["stoi"] = bstoi
         out["improvements"]["stoi"] = sscore - bstoi
+    if quality:
+        base_q = None
+        for k, name in enumerate(("segsnr", "fwsegsnr")):
+            out[name] = None
+            qid, qscore = select_best(specs, table, name)[(0, alg)]
+            if qid < 0:
+                continue
+            if base_q is None:
+                base_q = (quality_fn or _device_quality)(clean[0], noisy[0], sr)
+            out[name] = {"score": qscore, "params": dict(specs[qid][2]), "cell": int(qid),
+                         "snr": float(table[qid, 1])}
+            out["baseline"][name] = base_q[k] or 0
+            out["improvements"][name] = qscore - out["baseline"][name]
     return out
 
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
-              group=None, device=None, extended=False):
+              group=None, device=None, extended=False, quality=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
@@ -666,20 +746,27 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     (results.write_summary) under results_summary/.  Rank 0 writes.
     extended=True: scored and selected by extended STOI; the rows' stoi_* fields
     then hold ESTOI, each row carries "stoi_extended": True, and the file names
-    stay the same."""
+    stay the same.
+    quality=True: the cells are also scored by segSNR and fwSegSNR; the
+    fwSegSNR-best cell's waveform is written as ..._optimized_fwsegsnr.wav and
+    each row gains segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best,
+    best_params_fwsegsnr and snr_fwsegopt (means in summary_means.json).  The
+    segSNR winner is select_best(specs, table, "segsnr")'s."""
     import torch
     import torch.distributed as dist
     from . import results
     from .engine import Engine
-    from .metrics import StoiPlan
+    from .metrics import SegSnrPlan, StoiPlan
     grids = grids or ALGORITHM_GRIDS
     algorithms = list(algorithms or grids)
     specs = job_specs(len(noisy), algorithms, grids)
-    table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended)
+    table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
+                           quality=quality)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
     best_stoi = select_best(specs, table, "stoi")
+    best_fw = select_best(specs, table, "fwsegsnr") if quality else None
     eng = Engine()
     rows = []
     for pair, stem in enumerate(stems):
@@ -690,6 +777,10 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         plan = StoiPlan(torch.as_tensor(c[:m]).cuda().view(1, -1), extended=extended)
         nf = torch.as_tensor(n[:m].astype(np.float32)).cuda()
         stoi_noisy = _opt(plan.score(nf, [0], [0], clip=False)[0])
+        q_noisy = None
+        if quality:
+            qplan = SegSnrPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
+            q_noisy = [_opt(v) for v in qplan.score(nf, [0], [0], clip=False)[0]]
         x = torch.as_tensor(n).cuda().view(1, -1)
         cl = torch.as_tensor(c).cuda().view(1, -1)
         for alg in algorithms:
@@ -699,7 +790,8 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
             sid, sscore = best_stoi[(pair, alg)]
             out_dir = os.path.join(out_root, f"results_{alg}")
             os.makedirs(out_dir, exist_ok=True)
-            for tag, k in (("snr", cid), ("stoi", sid)):
+            fid, fscore = best_fw[(pair, alg)] if quality else (-1, None)
+            for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid)):
                 if k < 0:
                     continue
                 res = eng.run(x, [(0, alg, specs[k][2])], clean=cl, want_waveforms=True, align=True)
@@ -711,7 +803,12 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                 stem, alg, sr, snr_noisy, float(score), specs[cid][2], stoi_noisy=stoi_noisy,
                 stoi_best=None if sid < 0 else float(sscore),
                 stoi_params=None if sid < 0 else specs[sid][2],
-                snr_stoiopt=None if sid < 0 else float(table[sid, 1])))
+                snr_stoiopt=None if sid < 0 else float(table[sid, 1]),
+                **({} if not quality else dict(
+                    segsnr_noisy=q_noisy[0], fwsegsnr_noisy=q_noisy[1],
+                    fwsegsnr_best=None if fid < 0 else float(fscore),
+                    fwsegsnr_params=None if fid < 0 else specs[fid][2],
+                    snr_fwsegopt=None if fid < 0 else float(table[fid, 1])))))
             if extended:
                 rows[-1]["stoi_extended"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
