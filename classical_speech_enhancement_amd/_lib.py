@@ -1,5 +1,6 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
-include/cse_estoi.h, include/cse_mcra.h and include/cse_segsnr.h).
+include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h and
+include/cse_spp.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -18,7 +19,7 @@ CSE_OK = 0
 # NOISE_JOB_DTYPE == cse_noise_job_t, NoiseParams == cse_noise_params_t)
 ABI_VERSION = 5
 ALGO = {"NONE": -1, "SS": 0, "WIENER": 1, "MMSE": 2, "OMLSA": 3}
-NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "mcra": 3}
+NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "mcra": 3, "spp": 4}
 
 # numpy mirror of cse_cell_t (include/cse.h) — 96 bytes
 CELL_DTYPE = np.dtype([
@@ -57,6 +58,17 @@ class McraParams(ctypes.Structure):
 
 assert ctypes.sizeof(McraParams) == 40
 
+
+class SppParams(ctypes.Structure):
+    """cse_spp_params_t (include/cse_spp.h): the SPP-MMSE tracker's parameters."""
+    _fields_ = [("prior_h1", ctypes.c_double), ("xi_opt_db", ctypes.c_double),
+                ("alpha_pow", ctypes.c_double), ("alpha_ph", ctypes.c_double),
+                ("ph_max", ctypes.c_double), ("init_frames", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(SppParams) == 48
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -74,6 +86,8 @@ EXPORTS_MCRA = ("cse_mcra_default_params", "cse_noise_mcra")
 # include/cse_segsnr.h (segmental and frequency-weighted segmental SNR), likewise
 EXPORTS_SEGSNR = ("cse_segsnr_workspace_bytes", "cse_segsnr_prepare", "cse_segsnr_scratch_bytes",
                   "cse_segsnr_cells")
+# include/cse_spp.h (SPP-MMSE noise tracking), likewise
+EXPORTS_SPP = ("cse_spp_default_params", "cse_noise_spp")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -167,6 +181,10 @@ def load(path=LIB_PATH):
     lib.cse_mcra_default_params.argtypes = [P]
     lib.cse_noise_mcra.restype = i32
     lib.cse_noise_mcra.argtypes = [P, i64, i32, i32, P, f64, P, P]
+    lib.cse_spp_default_params.restype = None
+    lib.cse_spp_default_params.argtypes = [P]
+    lib.cse_noise_spp.restype = i32
+    lib.cse_noise_spp.argtypes = [P, i64, i32, i32, P, f64, P, P]
     lib.cse_segsnr_workspace_bytes.restype = i64
     lib.cse_segsnr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_segsnr_prepare.restype = i32

@@ -21,9 +21,10 @@ import torch
 from . import _lib
 # the planning names other modules and the tests import from here stay importable
 from .layout import (ALGO_COST, ALGOS, ALIGN_CORR_SAMPLES, ALIGN_MAX_LAG,  # noqa: F401
-                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, MCRA_DEFAULTS, SHORT, PlanLayout,
-                     Ref, canonical_algo, mcra_params, mcra_values, n_frames, noise_key,
-                     noise_params, pack_waves, route, route_slots, specs_by_n_fft)
+                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, MCRA_DEFAULTS, SHORT, SPP_DEFAULTS,
+                     PlanLayout, Ref, canonical_algo, mcra_params, mcra_values, n_frames,
+                     noise_key, noise_params, pack_waves, route, route_slots, specs_by_n_fft,
+                     spp_params, spp_values)
 
 
 def _ptr(t):
@@ -75,7 +76,9 @@ class Engine:
         :60).  true_noise: P is the power of STFT(noisy - clean) over the
         shorter length, fit to ``frames`` (default T') frames (:149-153).
         mcra: cse_noise_mcra (include/cse_mcra.h) -> [S, T, B] at any T; params
-        are alpha_s, alpha_d, alpha_p, delta, window_frames."""
+        are alpha_s, alpha_d, alpha_p, delta, window_frames.
+        spp: cse_noise_spp (include/cse_spp.h) -> [S, T, B] at any T; params are
+        prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames."""
         S, Tp, B = P.shape
         if method == "mcra":
             if frames is not None and int(frames) != Tp:
@@ -88,6 +91,18 @@ class Engine:
                 out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
             _lib.check(self.lib.cse_noise_mcra(_ptr(P), S, Tp, B, ctypes.byref(prm), float(eps),
                                                _ptr(out), _stream()), "cse_noise_mcra")
+            return out
+        if method == "spp":
+            if frames is not None and int(frames) != Tp:
+                raise ValueError("frames applies to true_noise only")
+            unknown = set(params) - set(SPP_DEFAULTS)
+            if unknown:
+                raise TypeError(f"spp takes no parameter {sorted(unknown)[0]!r}")
+            prm = spp_params(spp_values(params))
+            if out is None:
+                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
+            _lib.check(self.lib.cse_noise_spp(_ptr(P), S, Tp, B, ctypes.byref(prm), float(eps),
+                                              _ptr(out), _stream()), "cse_noise_spp")
             return out
         T = Tp if frames is None else int(frames)
         code = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "simple": 0}[method]
@@ -275,7 +290,7 @@ class GridPlan:
         if isinstance(a, Ref):
             buf = getattr(self, a.buf)
             return _at(buf[hop] if isinstance(buf, dict) else buf, a.off)
-        return ctypes.byref(a) if isinstance(a, (_lib.NoiseParams, _lib.McraParams)) else a
+        return ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
 
     def enhance(self):
         """THE HOT PATH launch: every cell of this n_fft, one kernel."""

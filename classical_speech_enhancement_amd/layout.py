@@ -99,13 +99,61 @@ def mcra_params(values):
     return prm
 
 
+# the SPP-MMSE tracker's parameters (include/cse_spp.h; Gerkmann & Hendriks 2012,
+# the paper's values).  Cell params carry them as spp_<name>.
+SPP_DEFAULTS = {"prior_h1": 0.5, "xi_opt_db": 15.0, "alpha_pow": 0.8, "alpha_ph": 0.9,
+                "ph_max": 0.99, "init_frames": 5}
+
+
+def spp_values(params, prefix=""):
+    """(prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames) read from
+    ``params`` under prefix + name, defaults where absent; raises ValueError for
+    what cse_noise_spp refuses, and for an init_frames that is no integer."""
+    prior, xi, a_pow, a_ph, ph_max = (float(params.get(prefix + k, SPP_DEFAULTS[k]))
+                                      for k in ("prior_h1", "xi_opt_db", "alpha_pow", "alpha_ph",
+                                                "ph_max"))
+    k = params.get(prefix + "init_frames", SPP_DEFAULTS["init_frames"])
+    for name, v in (("prior_h1", prior), ("ph_max", ph_max)):
+        if not 0.0 < v < 1.0:
+            raise ValueError(f"spp {name}={v} not in (0, 1)")
+    for name, a in (("alpha_pow", a_pow), ("alpha_ph", a_ph)):
+        if not 0.0 <= a < 1.0:
+            raise ValueError(f"spp {name}={a} not in [0, 1)")
+    if not math.isfinite(xi):
+        raise ValueError(f"spp xi_opt_db={xi} not finite")
+    if not (isinstance(k, (int, float, np.integer, np.floating)) and math.isfinite(k)
+            and k == int(k) and 1 <= int(k) < 2**31):
+        raise ValueError(f"spp init_frames={k} not an integer >= 1")
+    return (prior, xi, a_pow, a_ph, ph_max, int(k))
+
+
+def spp_params(values):
+    """cse_spp_params_t from spp_values' tuple."""
+    prm = _lib.SppParams()
+    (prm.prior_h1, prm.xi_opt_db, prm.alpha_pow, prm.alpha_ph, prm.ph_max,
+     prm.init_frames) = values
+    return prm
+
+
+# the trackers that go beyond the reference: method -> (values function, params
+# function); their values tuple is the estimator slot of a noise key
+TRACKERS = {"mcra": (mcra_values, mcra_params), "spp": (spp_values, spp_params)}
+
+
+def tracker_values(params):
+    """The values tuple of a cell whose noise_method is a tracker (its
+    parameters read as <method>_<name>), () for every other method."""
+    method = params["noise_method"]
+    return TRACKERS[method][0](params, method + "_") if method in TRACKERS else ()
+
+
 def noise_key(alg, params, T):
     """Which noise PSD array a cell reads, mirroring each algorithm's pipeline.
 
     Returns (method, pct, eps, expand, mu, inverse); pct is the estimator's
-    parameter slot: the percentile, or for mcra the mcra_values tuple
-    (noise_percentile does not enter: cells that differ only in it share one
-    estimate):
+    parameter slot: the percentile, or for mcra / spp the mcra_values /
+    spp_values tuple (noise_percentile does not enter: cells that differ only
+    in it share one estimate):
       - every algorithm estimates with the eps it passes (ss/wiener/omlsa 1e-10,
         mmse 1e-12: spectral_subtractor.py:17, wiener_filter.py:23, mmse.py:17,
         advanced_mmse.py:26);
@@ -116,9 +164,9 @@ def noise_key(alg, params, T):
         advanced_mmse.py:54-55), which ZERO-PADS frames 1..T-1 — frame 0 sees
         the estimate, later frames see 0 (SS) or, after OMLSA's smoothing,
         mu**t times it;
-      - mcra (no counterpart in the reference) is time-varying and takes
+      - mcra and spp (no counterpart in the reference) are time-varying and take
         min_tracking's place in each pipeline: smoothed by mmse/omlsa, inverted
-        with the algorithm's eps for Wiener/MMSE/OMLSA, as it is for SS;
+        with the algorithm's eps for Wiener/MMSE/OMLSA, as they are for SS;
       - mmse/omlsa smooth any time-varying estimate except true_noise
         (mmse.py:48-54, advanced_mmse.py:60-66); mu=None means no smoothing;
       - inverse: Wiener/MMSE/OMLSA read 1/max(N, eps) (their in-loop floor,
@@ -128,11 +176,11 @@ def noise_key(alg, params, T):
     """
     code, eps, _ = ALGOS[alg]
     method = params["noise_method"]
-    mcra = mcra_values(params, "mcra_") if method == "mcra" else None  # validated at any T
+    tracker = tracker_values(params)  # validated at any T
     if T < 5:
         method, pct = "simple", None
-    elif mcra is not None:  # time-varying, like min_tracking
-        pct = mcra
+    elif tracker:  # time-varying, like min_tracking
+        pct = tracker
     elif method == "percentile":
         pct = float(params["noise_percentile"])
     elif method in ("min_tracking", "true_noise"):
@@ -184,8 +232,7 @@ def specs_by_n_fft(S, L, specs, with_clean, want_g):
         if not 0 <= int(sig) < S:
             raise ValueError(f"signal index {sig} out of range")
         ck = (alg, hop, nf, p["noise_method"])
-        if ck[3] == "mcra":  # and per distinct parameter set
-            ck += mcra_values(p, "mcra_")
+        ck += tracker_values(p)  # and per distinct parameter set of mcra / spp
         if ck not in checked:  # per distinct (algorithm, hop, n_fft, method)
             r = route(nf, hop)
             if r is None:
@@ -300,8 +347,7 @@ class PlanLayout:
         for (_, _, alg, p) in self.items:
             hop = p["hop_length"]
             ck = (alg, hop, p["noise_method"], p.get("noise_percentile"), p.get("noise_mu"))
-            if ck[2] == "mcra":
-                ck += mcra_values(p, "mcra_")
+            ck += tracker_values(p)
             k = key_cache.get(ck)
             if k is None:
                 k = key_cache[ck] = (hop, noise_key(alg, p, n_frames(L, hop)))
@@ -390,9 +436,9 @@ class PlanLayout:
             if method == "simple":
                 calls.append(("cse_noise_estimate",
                               (0, P, S, T, B, 25.0, float(eps), raw(b), ws)))
-            elif method == "mcra":  # one call per (parameter set, eps)
-                calls.append(("cse_noise_mcra",
-                              (P, S, T, B, mcra_params(pct), float(eps), raw(b))))
+            elif method in TRACKERS:  # mcra, spp: one call per (parameter set, eps)
+                calls.append(("cse_noise_" + method,
+                              (P, S, T, B, TRACKERS[method][1](pct), float(eps), raw(b))))
             elif method == "true_noise":
                 prm = noise_params(src_frames=self.ptrue_shape[hop][1])
                 calls.append(("cse_noise_estimate_ex",

@@ -16,12 +16,15 @@ One estimator goes beyond the reference: noise_method="mcra" (minima-controlled
 recursive averaging, include/cse_mcra.h).  The four algorithm plugins take its
 parameters as a trailing keyword mcra={alpha_s, alpha_d, alpha_p, delta,
 window_frames} (defaults: the paper's); every other call means what it meant.
+So does noise_method="spp" (SPP-based MMSE tracking, include/cse_spp.h), with
+the trailing keyword spp={prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max,
+init_frames}.
 """
 
 import numpy as np
 import torch
 
-from .engine import MCRA_DEFAULTS, NOISE_PARAM_KEYS, Engine, n_frames
+from .engine import MCRA_DEFAULTS, NOISE_PARAM_KEYS, SPP_DEFAULTS, Engine, n_frames
 
 _ENGINE = None
 
@@ -47,12 +50,17 @@ def _dev(x):
     return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).cuda().view(1, -1)
 
 
-def _single(alg, noisy, clean, params, rule, mcra=None):
+def _single(alg, noisy, clean, params, rule, mcra=None, spp=None):
     if mcra:  # the tracker's parameters ride in the cell params as mcra_<name>
         unknown = set(mcra) - set(MCRA_DEFAULTS)
         if unknown:
             raise TypeError(f"mcra takes no parameter {sorted(unknown)[0]!r}")
         params.update(("mcra_" + k, v) for k, v in mcra.items())
+    if spp:  # likewise, as spp_<name>
+        unknown = set(spp) - set(SPP_DEFAULTS)
+        if unknown:
+            raise TypeError(f"spp takes no parameter {sorted(unknown)[0]!r}")
+        params.update(("spp_" + k, v) for k, v in spp.items())
     x = _mono(noisy, rule)
     if x.size == 0:  # the reference's reflect padding of an empty signal raises
         raise ValueError("can't extend empty axis 0 using modes other than 'constant' or 'empty'")
@@ -77,37 +85,39 @@ def _single(alg, noisy, clean, params, rule, mcra=None):
 
 
 def spectral_subtraction(noisy_audio, sr, alpha, beta, n_fft, hop_length, noise_percentile,
-                         noise_method, clean_audio=None, mcra=None):
+                         noise_method, clean_audio=None, mcra=None, spp=None):
     return _single("spectralSubtractor", noisy_audio, clean_audio,
                    dict(alpha=alpha, beta=beta, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method),
-                   "shorter", mcra)
+                   "shorter", mcra, spp)
 
 
 def wiener_filter(noisy_audio, sr, n_fft, hop_length, alpha, gain_floor, noise_percentile,
-                  noise_method, clean_audio=None, mcra=None):
+                  noise_method, clean_audio=None, mcra=None, spp=None):
     return _single("wiener", noisy_audio, clean_audio,
                    dict(alpha=alpha, gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method), "axis1",
-                   mcra)
+                   mcra, spp)
 
 
 def mmse(noisy_audio, sr, alpha, ksi_min, gain_min, gain_max, n_fft, hop_length,
          noise_percentile, noise_method, noise_mu=0.98, clean_audio=None, log=True,
-         log_every=50, mcra=None):
+         log_every=50, mcra=None, spp=None):
     return _single("mmse", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, gain_min=gain_min, gain_max=gain_max,
                         n_fft=n_fft, hop_length=hop_length, noise_percentile=noise_percentile,
-                        noise_method=noise_method, noise_mu=noise_mu), "axis1", mcra)
+                        noise_method=noise_method, noise_mu=noise_mu), "axis1", mcra,
+                   spp)
 
 
 def advanced_mmse(noisy_audio, sr, n_fft, hop_length, alpha, ksi_min, q, noise_mu, gain_floor,
-                  noise_percentile, noise_method, clean_audio=None, v_max=80.0, mcra=None):
+                  noise_percentile, noise_method, clean_audio=None, v_max=80.0, mcra=None,
+                  spp=None):
     return _single("omlsa", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, q=q, noise_mu=noise_mu,
                         gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method,
-                        v_max=v_max), "shorter", mcra)
+                        v_max=v_max), "shorter", mcra, spp)
 
 
 def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win_length=None,
@@ -124,7 +134,9 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
 
     method="mcra" (not in the reference; include/cse_mcra.h) returns (B,T):
     alpha_s, alpha_d, alpha_p, delta and window_frames come from the merged
-    dict, eps from **kwargs (default 1e-10)."""
+    dict, eps from **kwargs (default 1e-10).  method="spp" (include/cse_spp.h)
+    likewise, with prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max and
+    init_frames."""
     if window != "hann" or not center or pad_mode != "reflect" or (win_length or n_fft) != n_fft:
         raise NotImplementedError("only hann/center/reflect/win_length=n_fft is implemented")
     full = dict(estimator_params or {})
@@ -154,6 +166,11 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
         _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
         N = eng.noise_estimate("mcra", P, eps=kwargs.get("eps", 1e-10),
                                **{k: full[k] for k in MCRA_DEFAULTS if k in full})
+        return N[0].cpu().numpy().astype(np.float64).T
+    if method == "spp":
+        _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
+        N = eng.noise_estimate("spp", P, eps=kwargs.get("eps", 1e-10),
+                               **{k: full[k] for k in SPP_DEFAULTS if k in full})
         return N[0].cpu().numpy().astype(np.float64).T
     if method == "true_noise":
         clean = kwargs.get("clean_audio")
