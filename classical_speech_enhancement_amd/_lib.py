@@ -1,6 +1,6 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
-include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h and
-include/cse_spp.h).
+include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
+include/cse_spp.h and include/cse_minstat.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -19,7 +19,8 @@ CSE_OK = 0
 # NOISE_JOB_DTYPE == cse_noise_job_t, NoiseParams == cse_noise_params_t)
 ABI_VERSION = 5
 ALGO = {"NONE": -1, "SS": 0, "WIENER": 1, "MMSE": 2, "OMLSA": 3}
-NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "mcra": 3, "spp": 4}
+NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "mcra": 3, "spp": 4,
+         "minstat": 5}
 
 # numpy mirror of cse_cell_t (include/cse.h) — 96 bytes
 CELL_DTYPE = np.dtype([
@@ -69,6 +70,21 @@ class SppParams(ctypes.Structure):
 
 assert ctypes.sizeof(SppParams) == 48
 
+
+class MinstatParams(ctypes.Structure):
+    """cse_minstat_params_t (include/cse_minstat.h): the minimum-statistics
+    tracker's parameters."""
+    _fields_ = [("alpha_c", ctypes.c_double), ("alpha_c_floor", ctypes.c_double),
+                ("alpha_max", ctypes.c_double), ("alpha_min", ctypes.c_double),
+                ("snr_exp", ctypes.c_double), ("beta_max", ctypes.c_double),
+                ("av", ctypes.c_double), ("q_eq_min", ctypes.c_double),
+                ("q_eq_max", ctypes.c_double), ("slope_q", ctypes.c_double * 3),
+                ("slope_max", ctypes.c_double * 4), ("sub_windows", ctypes.c_int32),
+                ("sub_frames", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(MinstatParams) == 136
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -88,6 +104,8 @@ EXPORTS_SEGSNR = ("cse_segsnr_workspace_bytes", "cse_segsnr_prepare", "cse_segsn
                   "cse_segsnr_cells")
 # include/cse_spp.h (SPP-MMSE noise tracking), likewise
 EXPORTS_SPP = ("cse_spp_default_params", "cse_noise_spp")
+# include/cse_minstat.h (minimum-statistics noise tracking), likewise
+EXPORTS_MINSTAT = ("cse_minstat_default_params", "cse_noise_minstat")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -185,6 +203,10 @@ def load(path=LIB_PATH):
     lib.cse_spp_default_params.argtypes = [P]
     lib.cse_noise_spp.restype = i32
     lib.cse_noise_spp.argtypes = [P, i64, i32, i32, P, f64, P, P]
+    lib.cse_minstat_default_params.restype = None
+    lib.cse_minstat_default_params.argtypes = [P]
+    lib.cse_noise_minstat.restype = i32
+    lib.cse_noise_minstat.argtypes = [P, i64, i32, i32, P, f64, P, P]
     lib.cse_segsnr_workspace_bytes.restype = i64
     lib.cse_segsnr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_segsnr_prepare.restype = i32

@@ -21,10 +21,11 @@ import torch
 from . import _lib
 # the planning names other modules and the tests import from here stay importable
 from .layout import (ALGO_COST, ALGOS, ALIGN_CORR_SAMPLES, ALIGN_MAX_LAG,  # noqa: F401
-                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, MCRA_DEFAULTS, SHORT, SPP_DEFAULTS,
-                     PlanLayout, Ref, canonical_algo, mcra_params, mcra_values, n_frames,
-                     noise_key, noise_params, pack_waves, route, route_slots, specs_by_n_fft,
-                     spp_params, spp_values)
+                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, MCRA_DEFAULTS, MINSTAT_DEFAULTS,
+                     SHORT, SPP_DEFAULTS, PlanLayout, Ref, canonical_algo, mcra_params,
+                     mcra_values, minstat_params, minstat_values, n_frames, noise_key,
+                     noise_params, pack_waves, route, route_slots, specs_by_n_fft, spp_params,
+                     spp_values)
 
 
 def _ptr(t):
@@ -78,7 +79,9 @@ class Engine:
         mcra: cse_noise_mcra (include/cse_mcra.h) -> [S, T, B] at any T; params
         are alpha_s, alpha_d, alpha_p, delta, window_frames.
         spp: cse_noise_spp (include/cse_spp.h) -> [S, T, B] at any T; params are
-        prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames."""
+        prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames.
+        minstat: cse_noise_minstat (include/cse_minstat.h) -> [S, T, B] at any T;
+        params are the names of layout.MINSTAT_DEFAULTS."""
         S, Tp, B = P.shape
         if method == "mcra":
             if frames is not None and int(frames) != Tp:
@@ -103,6 +106,19 @@ class Engine:
                 out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
             _lib.check(self.lib.cse_noise_spp(_ptr(P), S, Tp, B, ctypes.byref(prm), float(eps),
                                               _ptr(out), _stream()), "cse_noise_spp")
+            return out
+        if method == "minstat":
+            if frames is not None and int(frames) != Tp:
+                raise ValueError("frames applies to true_noise only")
+            unknown = set(params) - set(MINSTAT_DEFAULTS)
+            if unknown:
+                raise TypeError(f"minstat takes no parameter {sorted(unknown)[0]!r}")
+            prm = minstat_params(minstat_values(params))
+            if out is None:
+                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
+            _lib.check(self.lib.cse_noise_minstat(_ptr(P), S, Tp, B, ctypes.byref(prm),
+                                                  float(eps), _ptr(out), _stream()),
+                       "cse_noise_minstat")
             return out
         T = Tp if frames is None else int(frames)
         code = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "simple": 0}[method]

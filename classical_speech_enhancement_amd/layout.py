@@ -135,9 +135,95 @@ def spp_params(values):
     return prm
 
 
+# the minimum-statistics tracker's parameters (include/cse_minstat.h; Martin
+# 2001, the paper's time constants at an 8-ms frame step: hop 128 at 16 kHz).
+# Cell params carry them as minstat_<name>.
+MINSTAT_DEFAULTS = {"alpha_c": 0.837, "alpha_c_floor": 0.7, "alpha_max": 0.98, "alpha_min": 0.548,
+                    "snr_exp": -0.125, "beta_max": 0.894, "av": 2.12, "q_eq_min": 2.0,
+                    "q_eq_max": 14.0, "slope_q": (0.03, 0.05, 0.06),
+                    "slope_max": (8.0, 4.0, 2.0, 1.2), "sub_windows": 8, "sub_frames": 24}
+_MINSTAT_SCALARS = ("alpha_c", "alpha_c_floor", "alpha_max", "alpha_min", "snr_exp", "beta_max",
+                    "av", "q_eq_min", "q_eq_max")
+
+
+def _whole(v, lo, hi):
+    return (isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+            and v == int(v) and lo <= int(v) <= hi)
+
+
+def minstat_values(params, prefix=""):
+    """(alpha_c, alpha_c_floor, alpha_max, alpha_min, snr_exp, beta_max, av,
+    q_eq_min, q_eq_max, slope_q, slope_max, sub_windows, sub_frames) read from
+    ``params`` under prefix + name, defaults where absent, slope_q and slope_max
+    as tuples; raises ValueError for what cse_noise_minstat refuses, and for
+    sub_windows / sub_frames that are no integers."""
+    get = lambda k: params.get(prefix + k, MINSTAT_DEFAULTS[k])  # noqa: E731
+    v = {k: float(get(k)) for k in _MINSTAT_SCALARS}
+    for k, n in (("slope_q", 3), ("slope_max", 4)):
+        try:
+            v[k] = tuple(float(x) for x in get(k))
+        except TypeError:
+            v[k] = ()
+        if len(v[k]) != n:
+            raise ValueError(f"minstat {k}={get(k)!r} not {n} numbers")
+    for k in ("alpha_c", "alpha_c_floor", "alpha_min", "beta_max"):
+        if not 0.0 <= v[k] < 1.0:
+            raise ValueError(f"minstat {k}={v[k]} not in [0, 1)")
+    if not 0.0 < v["alpha_max"] < 1.0:
+        raise ValueError(f"minstat alpha_max={v['alpha_max']} not in (0, 1)")
+    if not (math.isfinite(v["snr_exp"]) and v["snr_exp"] <= 0.0):
+        raise ValueError(f"minstat snr_exp={v['snr_exp']} not finite or > 0")
+    if not (math.isfinite(v["av"]) and v["av"] >= 0.0):
+        raise ValueError(f"minstat av={v['av']} not finite or < 0")
+    if not 2.0 <= v["q_eq_min"] <= v["q_eq_max"] < math.inf:
+        raise ValueError(f"minstat not 2 <= q_eq_min={v['q_eq_min']} <= "
+                         f"q_eq_max={v['q_eq_max']} < inf")
+    q = v["slope_q"]
+    if not (0.0 < q[0] < q[1] < q[2] < math.inf):
+        raise ValueError(f"minstat slope_q={q} not positive and strictly increasing")
+    if not all(math.isfinite(x) and x >= 1.0 for x in v["slope_max"]):
+        raise ValueError(f"minstat slope_max={v['slope_max']} not all finite and >= 1")
+    U, V = get("sub_windows"), get("sub_frames")
+    if not _whole(U, 1, 16):
+        raise ValueError(f"minstat sub_windows={U} not an integer in [1, 16]")
+    if not _whole(V, 2, 2**20):
+        raise ValueError(f"minstat sub_frames={V} not an integer in [2, 2^20]")
+    return tuple(v[k] for k in _MINSTAT_SCALARS) + (v["slope_q"], v["slope_max"], int(U), int(V))
+
+
+def minstat_params(values):
+    """cse_minstat_params_t from minstat_values' tuple."""
+    prm = _lib.MinstatParams()
+    for k, x in zip(_MINSTAT_SCALARS, values):
+        setattr(prm, k, x)
+    prm.slope_q[:] = values[9]
+    prm.slope_max[:] = values[10]
+    prm.sub_windows, prm.sub_frames = values[11], values[12]
+    return prm
+
+
+def minstat_time_constants(hop_length, sr):
+    """The parameter dict for a frame step of hop_length / sr seconds, from the
+    time constants behind MINSTAT_DEFAULTS (which are this at 128 / 16000):
+    alpha = exp(-step / tau), snr_exp = -step / 0.064, the sub-window's 0.192 s
+    in frames (at least 2), U = 8.  The thresholds on the degrees of freedom and
+    slope_max stay.  The plugins do not call it on their own."""
+    step = float(hop_length) / float(sr)
+    if not (step > 0.0 and math.isfinite(step)):
+        raise ValueError(f"hop_length={hop_length} sr={sr}: no frame step")
+    tau = {"alpha_c": 0.0449, "alpha_max": 0.392, "alpha_min": 0.0133, "beta_max": 0.0717}
+    out = dict(MINSTAT_DEFAULTS)
+    out.update((k, math.exp(-step / t)) for k, t in tau.items())
+    out["snr_exp"] = -step / 0.064
+    out["sub_windows"] = 8
+    out["sub_frames"] = max(2, int(round(0.192 / step)))
+    return out
+
+
 # the trackers that go beyond the reference: method -> (values function, params
 # function); their values tuple is the estimator slot of a noise key
-TRACKERS = {"mcra": (mcra_values, mcra_params), "spp": (spp_values, spp_params)}
+TRACKERS = {"mcra": (mcra_values, mcra_params), "spp": (spp_values, spp_params),
+            "minstat": (minstat_values, minstat_params)}
 
 
 def tracker_values(params):
@@ -151,8 +237,8 @@ def noise_key(alg, params, T):
     """Which noise PSD array a cell reads, mirroring each algorithm's pipeline.
 
     Returns (method, pct, eps, expand, mu, inverse); pct is the estimator's
-    parameter slot: the percentile, or for mcra / spp the mcra_values /
-    spp_values tuple (noise_percentile does not enter: cells that differ only
+    parameter slot: the percentile, or for mcra / spp / minstat the mcra_values /
+    spp_values / minstat_values tuple (noise_percentile does not enter: cells that differ only
     in it share one estimate):
       - every algorithm estimates with the eps it passes (ss/wiener/omlsa 1e-10,
         mmse 1e-12: spectral_subtractor.py:17, wiener_filter.py:23, mmse.py:17,
@@ -164,7 +250,7 @@ def noise_key(alg, params, T):
         advanced_mmse.py:54-55), which ZERO-PADS frames 1..T-1 — frame 0 sees
         the estimate, later frames see 0 (SS) or, after OMLSA's smoothing,
         mu**t times it;
-      - mcra and spp (no counterpart in the reference) are time-varying and take
+      - mcra, spp and minstat (no counterpart in the reference) are time-varying and take
         min_tracking's place in each pipeline: smoothed by mmse/omlsa, inverted
         with the algorithm's eps for Wiener/MMSE/OMLSA, as they are for SS;
       - mmse/omlsa smooth any time-varying estimate except true_noise
@@ -232,7 +318,7 @@ def specs_by_n_fft(S, L, specs, with_clean, want_g):
         if not 0 <= int(sig) < S:
             raise ValueError(f"signal index {sig} out of range")
         ck = (alg, hop, nf, p["noise_method"])
-        ck += tracker_values(p)  # and per distinct parameter set of mcra / spp
+        ck += tracker_values(p)  # and per distinct parameter set of a tracker
         if ck not in checked:  # per distinct (algorithm, hop, n_fft, method)
             r = route(nf, hop)
             if r is None:
@@ -436,7 +522,7 @@ class PlanLayout:
             if method == "simple":
                 calls.append(("cse_noise_estimate",
                               (0, P, S, T, B, 25.0, float(eps), raw(b), ws)))
-            elif method in TRACKERS:  # mcra, spp: one call per (parameter set, eps)
+            elif method in TRACKERS:  # mcra, spp, minstat: one call per (parameter set, eps)
                 calls.append(("cse_noise_" + method,
                               (P, S, T, B, TRACKERS[method][1](pct), float(eps), raw(b))))
             elif method == "true_noise":
