@@ -1,6 +1,6 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
-include/cse_spp.h and include/cse_minstat.h).
+include/cse_spp.h, include/cse_minstat.h and include/cse_imcra.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -20,7 +20,7 @@ CSE_OK = 0
 ABI_VERSION = 5
 ALGO = {"NONE": -1, "SS": 0, "WIENER": 1, "MMSE": 2, "OMLSA": 3}
 NOISE = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "mcra": 3, "spp": 4,
-         "minstat": 5}
+         "minstat": 5, "imcra": 6}
 
 # numpy mirror of cse_cell_t (include/cse.h) — 96 bytes
 CELL_DTYPE = np.dtype([
@@ -85,6 +85,19 @@ class MinstatParams(ctypes.Structure):
 
 assert ctypes.sizeof(MinstatParams) == 136
 
+
+class ImcraParams(ctypes.Structure):
+    """cse_imcra_params_t (include/cse_imcra.h): the IMCRA tracker's parameters."""
+    _fields_ = [("alpha", ctypes.c_double), ("alpha_s", ctypes.c_double),
+                ("alpha_d", ctypes.c_double), ("beta", ctypes.c_double),
+                ("b_min", ctypes.c_double), ("gamma0", ctypes.c_double),
+                ("gamma1", ctypes.c_double), ("zeta0", ctypes.c_double),
+                ("xi_min_db", ctypes.c_double), ("sub_windows", ctypes.c_int32),
+                ("sub_frames", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(ImcraParams) == 80
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -106,6 +119,8 @@ EXPORTS_SEGSNR = ("cse_segsnr_workspace_bytes", "cse_segsnr_prepare", "cse_segsn
 EXPORTS_SPP = ("cse_spp_default_params", "cse_noise_spp")
 # include/cse_minstat.h (minimum-statistics noise tracking), likewise
 EXPORTS_MINSTAT = ("cse_minstat_default_params", "cse_noise_minstat")
+# include/cse_imcra.h (IMCRA noise tracking), likewise
+EXPORTS_IMCRA = ("cse_imcra_default_params", "cse_noise_imcra")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -207,6 +222,10 @@ def load(path=LIB_PATH):
     lib.cse_minstat_default_params.argtypes = [P]
     lib.cse_noise_minstat.restype = i32
     lib.cse_noise_minstat.argtypes = [P, i64, i32, i32, P, f64, P, P]
+    lib.cse_imcra_default_params.restype = None
+    lib.cse_imcra_default_params.argtypes = [P]
+    lib.cse_noise_imcra.restype = i32
+    lib.cse_noise_imcra.argtypes = [P, i64, i32, i32, P, f64, P, P]
     lib.cse_segsnr_workspace_bytes.restype = i64
     lib.cse_segsnr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_segsnr_prepare.restype = i32

@@ -21,11 +21,11 @@ import torch
 from . import _lib
 # the planning names other modules and the tests import from here stay importable
 from .layout import (ALGO_COST, ALGOS, ALIGN_CORR_SAMPLES, ALIGN_MAX_LAG,  # noqa: F401
-                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, MCRA_DEFAULTS, MINSTAT_DEFAULTS,
-                     SHORT, SPP_DEFAULTS, PlanLayout, Ref, canonical_algo, mcra_params,
-                     mcra_values, minstat_params, minstat_values, n_frames, noise_key,
-                     noise_params, pack_waves, route, route_slots, specs_by_n_fft, spp_params,
-                     spp_values)
+                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, IMCRA_DEFAULTS, MAIN, MCRA_DEFAULTS,
+                     MINSTAT_DEFAULTS, SHORT, SPP_DEFAULTS, PlanLayout, Ref, canonical_algo,
+                     imcra_params, imcra_values, mcra_params, mcra_values, minstat_params,
+                     minstat_values, n_frames, noise_key, noise_params, pack_waves, route,
+                     route_slots, specs_by_n_fft, spp_params, spp_values)
 
 
 def _ptr(t):
@@ -81,7 +81,9 @@ class Engine:
         spp: cse_noise_spp (include/cse_spp.h) -> [S, T, B] at any T; params are
         prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames.
         minstat: cse_noise_minstat (include/cse_minstat.h) -> [S, T, B] at any T;
-        params are the names of layout.MINSTAT_DEFAULTS."""
+        params are the names of layout.MINSTAT_DEFAULTS.
+        imcra: cse_noise_imcra (include/cse_imcra.h) -> [S, T, B] at any T;
+        params are the names of layout.IMCRA_DEFAULTS."""
         S, Tp, B = P.shape
         if method == "mcra":
             if frames is not None and int(frames) != Tp:
@@ -119,6 +121,19 @@ class Engine:
             _lib.check(self.lib.cse_noise_minstat(_ptr(P), S, Tp, B, ctypes.byref(prm),
                                                   float(eps), _ptr(out), _stream()),
                        "cse_noise_minstat")
+            return out
+        if method == "imcra":
+            if frames is not None and int(frames) != Tp:
+                raise ValueError("frames applies to true_noise only")
+            unknown = set(params) - set(IMCRA_DEFAULTS)
+            if unknown:
+                raise TypeError(f"imcra takes no parameter {sorted(unknown)[0]!r}")
+            prm = imcra_params(imcra_values(params))
+            if out is None:
+                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
+            _lib.check(self.lib.cse_noise_imcra(_ptr(P), S, Tp, B, ctypes.byref(prm),
+                                                float(eps), _ptr(out), _stream()),
+                       "cse_noise_imcra")
             return out
         T = Tp if frames is None else int(frames)
         code = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "simple": 0}[method]

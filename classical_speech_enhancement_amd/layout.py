@@ -220,26 +220,91 @@ def minstat_time_constants(hop_length, sr):
     return out
 
 
+# the IMCRA tracker's parameters (include/cse_imcra.h; Cohen 2003, the paper's
+# values for n_fft 512 / hop 128 at 16 kHz).  Cell params carry them as
+# imcra_<name>.
+IMCRA_DEFAULTS = {"alpha": 0.92, "alpha_s": 0.9, "alpha_d": 0.85, "beta": 1.47, "b_min": 1.66,
+                  "gamma0": 4.6, "gamma1": 3.0, "zeta0": 1.67, "xi_min_db": -18.0,
+                  "sub_windows": 8, "sub_frames": 15}
+_IMCRA_SCALARS = ("alpha", "alpha_s", "alpha_d", "beta", "b_min", "gamma0", "gamma1", "zeta0",
+                  "xi_min_db")
+
+
+def imcra_values(params, prefix=""):
+    """(alpha, alpha_s, alpha_d, beta, b_min, gamma0, gamma1, zeta0, xi_min_db,
+    sub_windows, sub_frames) read from ``params`` under prefix + name, defaults
+    where absent; raises ValueError for what cse_noise_imcra refuses, and for
+    sub_windows / sub_frames that are no integers."""
+    get = lambda k: params.get(prefix + k, IMCRA_DEFAULTS[k])  # noqa: E731
+    v = {k: float(get(k)) for k in _IMCRA_SCALARS}
+    for k in ("alpha", "alpha_s", "alpha_d"):
+        if not 0.0 <= v[k] < 1.0:
+            raise ValueError(f"imcra {k}={v[k]} not in [0, 1)")
+    for k in ("beta", "b_min", "gamma0", "zeta0"):
+        if not 0.0 < v[k] < math.inf:
+            raise ValueError(f"imcra {k}={v[k]} not finite and > 0")
+    if not 1.0 < v["gamma1"] < math.inf:
+        raise ValueError(f"imcra gamma1={v['gamma1']} not finite and > 1")
+    if not math.isfinite(v["xi_min_db"]):
+        raise ValueError(f"imcra xi_min_db={v['xi_min_db']} not finite")
+    U, V = get("sub_windows"), get("sub_frames")
+    if not _whole(U, 1, 16):
+        raise ValueError(f"imcra sub_windows={U} not an integer in [1, 16]")
+    if not _whole(V, 1, 2**20):
+        raise ValueError(f"imcra sub_frames={V} not an integer in [1, 2^20]")
+    return tuple(v[k] for k in _IMCRA_SCALARS) + (int(U), int(V))
+
+
+def imcra_params(values):
+    """cse_imcra_params_t from imcra_values' tuple."""
+    prm = _lib.ImcraParams()
+    for k, x in zip(_IMCRA_SCALARS + ("sub_windows", "sub_frames"), values):
+        setattr(prm, k, x)
+    return prm
+
+
+def imcra_time_constants(hop_length, sr):
+    """The parameter dict for a frame step of hop_length / sr seconds, from the
+    time constants behind IMCRA_DEFAULTS (which are this at 128 / 16000, exactly):
+    alpha, alpha_s and alpha_d become exp(-step / tau) with tau = -0.008 /
+    log(default), that is default ** (step / 0.008); the sub-window's 0.12 s in
+    frames (at least 1), U = 8.  beta, b_min and the thresholds stay.  The
+    plugins do not call it on their own."""
+    step = float(hop_length) / float(sr)
+    if not (step > 0.0 and math.isfinite(step)):
+        raise ValueError(f"hop_length={hop_length} sr={sr}: no frame step")
+    out = dict(IMCRA_DEFAULTS)
+    out.update((k, IMCRA_DEFAULTS[k] ** (step / 0.008)) for k in ("alpha", "alpha_s", "alpha_d"))
+    out["sub_windows"] = 8
+    out["sub_frames"] = max(1, int(math.floor(0.12 / step + 0.5)))
+    return out
+
+
 # the trackers that go beyond the reference: method -> (values function, params
 # function); their values tuple is the estimator slot of a noise key
 TRACKERS = {"mcra": (mcra_values, mcra_params), "spp": (spp_values, spp_params),
             "minstat": (minstat_values, minstat_params)}
+# TRACKERS keeps the three names it was published with (callers and
+# tests/test_minstat_host.py compare its key set); the registry that noise keys
+# and call lists are built from is ALL_TRACKERS, which holds every tracker
+ALL_TRACKERS = dict(TRACKERS, imcra=(imcra_values, imcra_params))
 
 
 def tracker_values(params):
     """The values tuple of a cell whose noise_method is a tracker (its
     parameters read as <method>_<name>), () for every other method."""
     method = params["noise_method"]
-    return TRACKERS[method][0](params, method + "_") if method in TRACKERS else ()
+    return ALL_TRACKERS[method][0](params, method + "_") if method in ALL_TRACKERS else ()
 
 
 def noise_key(alg, params, T):
     """Which noise PSD array a cell reads, mirroring each algorithm's pipeline.
 
     Returns (method, pct, eps, expand, mu, inverse); pct is the estimator's
-    parameter slot: the percentile, or for mcra / spp / minstat the mcra_values /
-    spp_values / minstat_values tuple (noise_percentile does not enter: cells that differ only
-    in it share one estimate):
+    parameter slot: the percentile, or for mcra / spp / minstat / imcra the
+    mcra_values / spp_values / minstat_values / imcra_values tuple
+    (noise_percentile does not enter: cells that differ only in it share one
+    estimate):
       - every algorithm estimates with the eps it passes (ss/wiener/omlsa 1e-10,
         mmse 1e-12: spectral_subtractor.py:17, wiener_filter.py:23, mmse.py:17,
         advanced_mmse.py:26);
@@ -250,8 +315,8 @@ def noise_key(alg, params, T):
         advanced_mmse.py:54-55), which ZERO-PADS frames 1..T-1 — frame 0 sees
         the estimate, later frames see 0 (SS) or, after OMLSA's smoothing,
         mu**t times it;
-      - mcra, spp and minstat (no counterpart in the reference) are time-varying and take
-        min_tracking's place in each pipeline: smoothed by mmse/omlsa, inverted
+      - mcra, spp, minstat and imcra (no counterpart in the reference) are
+        time-varying and take min_tracking's place in each pipeline: smoothed by mmse/omlsa, inverted
         with the algorithm's eps for Wiener/MMSE/OMLSA, as they are for SS;
       - mmse/omlsa smooth any time-varying estimate except true_noise
         (mmse.py:48-54, advanced_mmse.py:60-66); mu=None means no smoothing;
@@ -522,9 +587,9 @@ class PlanLayout:
             if method == "simple":
                 calls.append(("cse_noise_estimate",
                               (0, P, S, T, B, 25.0, float(eps), raw(b), ws)))
-            elif method in TRACKERS:  # mcra, spp, minstat: one call per (parameter set, eps)
+            elif method in ALL_TRACKERS:  # mcra, spp, ...: one call per (parameter set, eps)
                 calls.append(("cse_noise_" + method,
-                              (P, S, T, B, TRACKERS[method][1](pct), float(eps), raw(b))))
+                              (P, S, T, B, ALL_TRACKERS[method][1](pct), float(eps), raw(b))))
             elif method == "true_noise":
                 prm = noise_params(src_frames=self.ptrue_shape[hop][1])
                 calls.append(("cse_noise_estimate_ex",

@@ -61,8 +61,8 @@ ALGORITHM_GRIDS = {
 def grids_with_noise_methods(methods, grids=None):
     """Copies of the grids (default ALGORITHM_GRIDS) with the noise_method axis
     replaced by ``methods``, e.g. ("percentile", "min_tracking", "mcra", "spp",
-    "minstat"): for search.job_specs / run_grid / run_sweep (grids=...).  The default grids,
-    and so their cell ids, stay as they are."""
+    "minstat", "imcra"): for search.job_specs / run_grid / run_sweep
+    (grids=...).  The default grids, and so their cell ids, stay as they are."""
     methods = list(methods)
     if not methods:
         raise ValueError("no noise method given")

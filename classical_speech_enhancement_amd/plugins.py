@@ -20,14 +20,16 @@ So does noise_method="spp" (SPP-based MMSE tracking, include/cse_spp.h), with
 the trailing keyword spp={prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max,
 init_frames}, and noise_method="minstat" (minimum statistics,
 include/cse_minstat.h), with the trailing keyword minstat={...} (the names of
-layout.MINSTAT_DEFAULTS; defaults: the paper's time constants at an 8-ms step).
+layout.MINSTAT_DEFAULTS; defaults: the paper's time constants at an 8-ms step),
+and noise_method="imcra" (improved MCRA, include/cse_imcra.h), with the trailing
+keyword imcra={...} (the names of layout.IMCRA_DEFAULTS; defaults: the paper's).
 """
 
 import numpy as np
 import torch
 
-from .engine import (MCRA_DEFAULTS, MINSTAT_DEFAULTS, NOISE_PARAM_KEYS, SPP_DEFAULTS, Engine,
-                     n_frames)
+from .engine import (IMCRA_DEFAULTS, MCRA_DEFAULTS, MINSTAT_DEFAULTS, NOISE_PARAM_KEYS,
+                     SPP_DEFAULTS, Engine, n_frames)
 
 _ENGINE = None
 
@@ -53,7 +55,7 @@ def _dev(x):
     return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).cuda().view(1, -1)
 
 
-def _single(alg, noisy, clean, params, rule, mcra=None, spp=None, minstat=None):
+def _single(alg, noisy, clean, params, rule, mcra=None, spp=None, minstat=None, imcra=None):
     if mcra:  # the tracker's parameters ride in the cell params as mcra_<name>
         unknown = set(mcra) - set(MCRA_DEFAULTS)
         if unknown:
@@ -69,6 +71,11 @@ def _single(alg, noisy, clean, params, rule, mcra=None, spp=None, minstat=None):
         if unknown:
             raise TypeError(f"minstat takes no parameter {sorted(unknown)[0]!r}")
         params.update(("minstat_" + k, v) for k, v in minstat.items())
+    if imcra:  # likewise, as imcra_<name>
+        unknown = set(imcra) - set(IMCRA_DEFAULTS)
+        if unknown:
+            raise TypeError(f"imcra takes no parameter {sorted(unknown)[0]!r}")
+        params.update(("imcra_" + k, v) for k, v in imcra.items())
     x = _mono(noisy, rule)
     if x.size == 0:  # the reference's reflect padding of an empty signal raises
         raise ValueError("can't extend empty axis 0 using modes other than 'constant' or 'empty'")
@@ -93,39 +100,40 @@ def _single(alg, noisy, clean, params, rule, mcra=None, spp=None, minstat=None):
 
 
 def spectral_subtraction(noisy_audio, sr, alpha, beta, n_fft, hop_length, noise_percentile,
-                         noise_method, clean_audio=None, mcra=None, spp=None, minstat=None):
+                         noise_method, clean_audio=None, mcra=None, spp=None, minstat=None,
+                         imcra=None):
     return _single("spectralSubtractor", noisy_audio, clean_audio,
                    dict(alpha=alpha, beta=beta, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method),
-                   "shorter", mcra, spp, minstat)
+                   "shorter", mcra, spp, minstat, imcra)
 
 
 def wiener_filter(noisy_audio, sr, n_fft, hop_length, alpha, gain_floor, noise_percentile,
-                  noise_method, clean_audio=None, mcra=None, spp=None, minstat=None):
+                  noise_method, clean_audio=None, mcra=None, spp=None, minstat=None, imcra=None):
     return _single("wiener", noisy_audio, clean_audio,
                    dict(alpha=alpha, gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method), "axis1",
-                   mcra, spp, minstat)
+                   mcra, spp, minstat, imcra)
 
 
 def mmse(noisy_audio, sr, alpha, ksi_min, gain_min, gain_max, n_fft, hop_length,
          noise_percentile, noise_method, noise_mu=0.98, clean_audio=None, log=True,
-         log_every=50, mcra=None, spp=None, minstat=None):
+         log_every=50, mcra=None, spp=None, minstat=None, imcra=None):
     return _single("mmse", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, gain_min=gain_min, gain_max=gain_max,
                         n_fft=n_fft, hop_length=hop_length, noise_percentile=noise_percentile,
                         noise_method=noise_method, noise_mu=noise_mu), "axis1", mcra,
-                   spp, minstat)
+                   spp, minstat, imcra)
 
 
 def advanced_mmse(noisy_audio, sr, n_fft, hop_length, alpha, ksi_min, q, noise_mu, gain_floor,
                   noise_percentile, noise_method, clean_audio=None, v_max=80.0, mcra=None,
-                  spp=None, minstat=None):
+                  spp=None, minstat=None, imcra=None):
     return _single("omlsa", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, q=q, noise_mu=noise_mu,
                         gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method,
-                        v_max=v_max), "shorter", mcra, spp, minstat)
+                        v_max=v_max), "shorter", mcra, spp, minstat, imcra)
 
 
 def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win_length=None,
@@ -144,8 +152,9 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
     alpha_s, alpha_d, alpha_p, delta and window_frames come from the merged
     dict, eps from **kwargs (default 1e-10).  method="spp" (include/cse_spp.h)
     likewise, with prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max and
-    init_frames, and method="minstat" (include/cse_minstat.h) with the names of
-    layout.MINSTAT_DEFAULTS."""
+    init_frames, method="minstat" (include/cse_minstat.h) with the names of
+    layout.MINSTAT_DEFAULTS and method="imcra" (include/cse_imcra.h) with those
+    of layout.IMCRA_DEFAULTS."""
     if window != "hann" or not center or pad_mode != "reflect" or (win_length or n_fft) != n_fft:
         raise NotImplementedError("only hann/center/reflect/win_length=n_fft is implemented")
     full = dict(estimator_params or {})
@@ -185,6 +194,11 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
         _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
         N = eng.noise_estimate("minstat", P, eps=kwargs.get("eps", 1e-10),
                                **{k: full[k] for k in MINSTAT_DEFAULTS if k in full})
+        return N[0].cpu().numpy().astype(np.float64).T
+    if method == "imcra":
+        _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
+        N = eng.noise_estimate("imcra", P, eps=kwargs.get("eps", 1e-10),
+                               **{k: full[k] for k in IMCRA_DEFAULTS if k in full})
         return N[0].cpu().numpy().astype(np.float64).T
     if method == "true_noise":
         clean = kwargs.get("clean_audio")

@@ -125,7 +125,7 @@ class JobSpecs(list):
         """For each cell of one algorithm's grid, the first grid cell the engine
         computes identically for signals of this length: same n_fft, hop and
         algorithm parameters and the same noise PSD (engine.noise_key — e.g.
-        min_tracking, true_noise, mcra, spp and minstat ignore noise_percentile).  The
+        min_tracking, true_noise and the trackers ignore noise_percentile).  The
         noise key decides, not the method's name: a method whose key leaves
         noise_percentile out is deduplicated without being named here."""
         key = (alg_index, int(length))

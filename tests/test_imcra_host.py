@@ -1,0 +1,359 @@
+"""IMCRA noise tracking, the parts that need no GPU: the numpy restatement's own
+properties (tests/_imcra_ref.py, the definition of include/cse_imcra.h) and its
+second E1, the two entry points' declarations, exports and argument checks, and
+the layout: the parameter tuple, the noise key, the call list and the time
+constants at another frame step."""
+
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _imcra_ref
+from classical_speech_enhancement_amd import _lib, layout, parameter_ranges, search
+
+HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "cse_imcra.h")
+SCALARS = ("alpha", "alpha_s", "alpha_d", "beta", "b_min", "gamma0", "gamma1", "zeta0",
+           "xi_min_db")
+NAMES = SCALARS + ("sub_windows", "sub_frames")
+DEFAULT_VALUES = (0.92, 0.9, 0.85, 1.47, 1.66, 4.6, 3.0, 1.67, -18.0, 8, 15)
+SIZE = 80
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _lib.load()
+
+
+@pytest.fixture(scope="module")
+def stationary():
+    """200 frames of stationary exponential power of mean 1, made once."""
+    return np.random.default_rng(0).exponential(size=(200, 129))
+
+
+# ---------------------------------------------------------------- restatement
+@pytest.mark.parametrize("eps", (1e-10, 1e-12))
+def test_zero_power_returns_eps(eps):
+    N = _imcra_ref.imcra(np.zeros((130, 33)), eps)
+    assert N.dtype == np.float32 and np.array_equal(N, np.full((130, 33), np.float32(eps)))
+
+
+def test_constant_power_gives_the_constant_then_beta_times_it():
+    N = _imcra_ref.imcra(np.full((300, 33), 3.7))
+    assert N.dtype == np.float32 and N.shape == (300, 33)
+    np.testing.assert_allclose(N[0], 3.7, rtol=2.0 ** -23, atol=0)
+    np.testing.assert_allclose(N[1:], 1.47 * 3.7, rtol=2.0 ** -23, atol=0)
+
+
+def test_a_fall_is_followed_within_sixty_frames(stationary):
+    """/ 100 from frame 60 of 200 on: by frame 120 the mean estimate is within a
+    factor 1.5 of the new floor."""
+    dn = stationary.copy()
+    dn[60:] *= 0.01
+    N = _imcra_ref.imcra(dn)
+    m = float(N[120].mean())
+    print("frame mean at 120 over the new floor:", m / 0.01)
+    assert 0.01 / 1.5 <= m <= 0.01 * 1.5
+
+
+def test_a_rise_is_followed_after_the_window(stationary):
+    """x 100 from frame 60 on, U = 2, V = 4: the estimate passes half the new
+    floor within 3 U V + 20 frames, and not before U V (the second pass has
+    nothing to average until the first pass's minimum has forgotten the old
+    floor)."""
+    up = stationary.copy()
+    up[60:] *= 100.0
+    m = _imcra_ref.imcra(up, sub_windows=2, sub_frames=4).mean(axis=1)
+    first = int(np.argmax(m > 50.0))
+    print("frames after the rise until the mean passes half the new floor:", first - 60)
+    assert m[first] > 50.0
+    assert 60 + 2 * 4 <= first <= 60 + 3 * 2 * 4 + 20
+
+
+def test_non_default_parameters_change_the_output(stationary):
+    P = stationary.copy()
+    P[80:120] *= 40.0
+    base = _imcra_ref.imcra(P)
+    for k, v in dict(alpha=0.85, alpha_s=0.8, alpha_d=0.9, beta=1.2, b_min=1.4, gamma0=3.5,
+                     gamma1=2.5, zeta0=1.5, xi_min_db=-5.0, sub_windows=5, sub_frames=6).items():
+        assert not np.array_equal(_imcra_ref.imcra(P, **{k: v}), base), k
+    with pytest.raises(TypeError):
+        _imcra_ref.imcra(P, window_frames=3)
+    assert _imcra_ref.DEFAULTS == layout.IMCRA_DEFAULTS
+
+
+def test_batch_equals_the_signals_alone_and_stats(stationary):
+    P = stationary[:40].copy()
+    P[20:] *= 100.0
+    Q = 2.0 * stationary[40:80]
+    st, sp, sq = {}, {}, {}
+    N2 = _imcra_ref.imcra(np.stack([P, Q]), stats=st)
+    assert N2.shape == (2, 40, 129)
+    assert np.array_equal(N2[0], _imcra_ref.imcra(P, stats=sp))
+    assert np.array_equal(N2[1], _imcra_ref.imcra(Q, stats=sq))
+    assert set(st) == {"margin", "i1", "i0", "q0", "qf", "q1"}
+    assert st["margin"] == min(sp["margin"], sq["margin"]) >= 1e-9
+    for k in ("i1", "i0", "q0", "qf", "q1"):
+        assert st[k] == sp[k] + sq[k]
+    assert st["i1"] + st["i0"] == st["q0"] + st["qf"] + st["q1"] == 2 * 40 * 129
+    assert sp["i0"] >= 1 and sp["i1"] >= 1 and sp["qf"] >= 1
+    # T = 1: the output is the first frame
+    np.testing.assert_array_equal(_imcra_ref.imcra(P[:1])[0], P[0].astype(np.float32))
+
+
+def test_second_e1_against_scipy():
+    from scipy.special import exp1
+    v = np.concatenate([np.logspace(-300, math.log10(700.0), 20001),
+                        np.nextafter(1.0, [0.0, 2.0]), [1.0, 700.0]])
+    want = exp1(v)
+    err = float(np.max(np.abs(_imcra_ref.e1_plain(v) - want) / want))
+    print("second E1 against scipy.special.exp1, max relative error:", err)
+    assert err <= 1e-13
+    # and the restatement runs on it
+    P = np.random.default_rng(1).exponential(size=(30, 33))
+    a, b = _imcra_ref.imcra(P), _imcra_ref.imcra(P, e1=_imcra_ref.e1_plain)
+    assert np.max(np.abs(a.astype(np.float64) - b) / a) <= 2.0 ** -23
+
+
+# ------------------------------------------------------------------------ ABI
+def test_header_declares_the_exports(lib):
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names = set(re.findall(r"\b(cse_[a-z0-9_]+)\s*\(", text))
+    assert names == set(_lib.EXPORTS_IMCRA) == {"cse_imcra_default_params", "cse_noise_imcra"}
+    assert '#include "cse.h"' in text
+    assert not set(_lib.EXPORTS_IMCRA) & (set(_lib.EXPORTS) | set(_lib.EXPORTS_ESTOI) |
+                                          set(_lib.EXPORTS_MCRA) | set(_lib.EXPORTS_SEGSNR) |
+                                          set(_lib.EXPORTS_SPP) | set(_lib.EXPORTS_MINSTAT))
+    for n in _lib.EXPORTS_IMCRA:
+        assert hasattr(lib, n), n
+    assert lib.cse_version() == _lib.ABI_VERSION == 5
+    assert _lib.NOISE["imcra"] == 6 and "#define CSE_NOISE_IMCRA 6" in text
+    assert sorted(_lib.NOISE.values()) == list(range(7))
+
+
+def _as_tuple(prm):
+    return tuple(getattr(prm, n) for n in NAMES)
+
+
+def test_struct_size_offsets_and_defaults(lib):
+    assert ctypes.sizeof(_lib.ImcraParams) == SIZE
+    assert [f[0] for f in _lib.ImcraParams._fields_] == list(NAMES)
+    for i, n in enumerate(SCALARS):  # nine doubles, then two int32: the header's order
+        assert getattr(_lib.ImcraParams, n).offset == 8 * i
+        assert getattr(_lib.ImcraParams, n).size == 8
+    assert (_lib.ImcraParams.sub_windows.offset, _lib.ImcraParams.sub_frames.offset) == (72, 76)
+    head = open(HEADER).read()
+    assert "} cse_imcra_params_t; /* 80 bytes */" in head
+    fields = re.findall(r"^\s+(?:double|int32_t)\s+(\w+);", head, flags=re.M)
+    assert fields == list(NAMES)
+    # the C struct's size: default_params fills a guarded buffer of 80 bytes exactly
+    buf = (ctypes.c_ubyte * (SIZE + 8))(*([0xAB] * (SIZE + 8)))
+    lib.cse_imcra_default_params(ctypes.byref(buf))
+    assert bytes(buf[SIZE:]) == b"\xab" * 8
+    assert b"\xab" * 4 not in bytes(buf[:SIZE])
+    got = _as_tuple(_lib.ImcraParams.from_buffer_copy(bytes(buf[:SIZE])))
+    assert got == DEFAULT_VALUES
+    assert got == tuple(layout.IMCRA_DEFAULTS[k] for k in NAMES) == layout.imcra_values({})
+    assert got == tuple(_imcra_ref.DEFAULTS[k] for k in NAMES)
+    assert bytes(layout.imcra_params(layout.imcra_values({}))) == bytes(buf[:SIZE])
+    lib.cse_imcra_default_params(None)  # ignored
+
+
+def _call(lib, P=16, n_sig=0, T=10, B=257, prm="default", eps=1e-10, N=16, **fields):
+    """cse_noise_imcra with n_sig = 0 by default: every check runs, nothing is
+    launched."""
+    if prm == "default":
+        prm = _lib.ImcraParams()
+        lib.cse_imcra_default_params(ctypes.byref(prm))
+        for k, v in fields.items():
+            setattr(prm, k, v)
+        prm = ctypes.byref(prm)
+    return lib.cse_noise_imcra(ctypes.c_void_p(P) if P else None, n_sig, T, B, prm, eps,
+                               ctypes.c_void_p(N) if N else None, None)
+
+
+NAN, INF = math.nan, math.inf
+BAD_FIELDS = [
+    dict(alpha=-1e-9), dict(alpha=1.0), dict(alpha=NAN), dict(alpha_s=-0.1), dict(alpha_s=1.0),
+    dict(alpha_s=NAN), dict(alpha_d=-0.1), dict(alpha_d=1.0), dict(alpha_d=NAN),
+    dict(beta=0.0), dict(beta=-1.0), dict(beta=INF), dict(beta=NAN),
+    dict(b_min=0.0), dict(b_min=INF), dict(b_min=NAN),
+    dict(gamma0=0.0), dict(gamma0=INF), dict(gamma0=NAN),
+    dict(zeta0=0.0), dict(zeta0=-2.0), dict(zeta0=INF), dict(zeta0=NAN),
+    dict(gamma1=1.0), dict(gamma1=0.5), dict(gamma1=INF), dict(gamma1=NAN),
+    dict(xi_min_db=INF), dict(xi_min_db=-INF), dict(xi_min_db=NAN),
+    dict(sub_windows=0), dict(sub_windows=17), dict(sub_windows=-1), dict(sub_frames=0),
+    dict(sub_frames=2 ** 20 + 1), dict(sub_frames=-5)]
+_ids = lambda d: "-".join(f"{k}={v}" for k, v in d.items())  # noqa: E731
+
+
+@pytest.mark.parametrize("bad", [dict(P=None), dict(N=None), dict(prm=None), dict(n_sig=-1),
+                                 dict(T=0), dict(B=32), dict(B=2050)] + BAD_FIELDS, ids=_ids)
+def test_argument_checks(lib, bad):
+    assert _call(lib, **bad) == -1
+    assert b"cse_noise_imcra" in lib.cse_last_error(), lib.cse_last_error()
+
+
+def test_no_signals_launch_nothing(lib):
+    assert _call(lib) == 0
+    assert _call(lib, B=33, T=1, alpha=0.0, alpha_s=0.0, alpha_d=0.0, sub_windows=1,
+                 sub_frames=1) == 0
+    assert _call(lib, B=2049, gamma1=1.0000001, xi_min_db=-300.0, sub_windows=16,
+                 sub_frames=2 ** 20) == 0
+
+
+# --------------------------------------------------------------------- layout
+@pytest.mark.parametrize("bad", BAD_FIELDS + [dict(sub_windows=2.5), dict(sub_frames=NAN),
+                                              dict(sub_frames=7.5)], ids=_ids)
+def test_imcra_values_refuses_what_the_library_refuses(bad):
+    (name, _), = bad.items()
+    with pytest.raises(ValueError, match="imcra " + name + "="):
+        layout.imcra_values(bad)
+    cell = _cell("wiener", "imcra", **{"imcra_" + k: v for k, v in bad.items()})[2]
+    with pytest.raises(ValueError, match="imcra"):
+        layout.noise_key("wiener", cell, 63)
+    with pytest.raises(ValueError, match="imcra"):  # at any T, the simple path included
+        layout.noise_key("wiener", cell, 3)
+
+
+def test_imcra_values_is_hashable_and_reads_the_prefix():
+    v = layout.imcra_values({"imcra_beta": 1.2, "imcra_sub_frames": np.int64(12), "beta": 9.0,
+                             "imcra_gamma1": 2}, "imcra_")
+    assert v == (0.92, 0.9, 0.85, 1.2, 1.66, 4.6, 2.0, 1.67, -18.0, 8, 12)
+    assert hash(v) == hash(tuple(v)) and isinstance(v[10], int) and isinstance(v[6], float)
+    prm = layout.imcra_params(v)
+    assert isinstance(prm, _lib.ImcraParams) and _as_tuple(prm) == v
+    assert layout.ALL_TRACKERS["imcra"] == (layout.imcra_values, layout.imcra_params)
+    assert set(layout.ALL_TRACKERS) >= set(layout.TRACKERS) | {"imcra"}
+    assert all(layout.ALL_TRACKERS[k] == v for k, v in layout.TRACKERS.items())
+    assert layout.tracker_values({"noise_method": "imcra", "imcra_beta": 1.2}) == \
+        DEFAULT_VALUES[:3] + (1.2,) + DEFAULT_VALUES[4:]
+    assert layout.tracker_values({"noise_method": "imcra"}) == DEFAULT_VALUES
+    assert layout.tracker_values({"noise_method": "percentile", "imcra_beta": 1.2}) == ()
+    # a cell of another tracker does not read imcra_ names, bad ones included
+    assert layout.tracker_values({"noise_method": "minstat", "imcra_beta": -1.0}) == \
+        layout.minstat_values({})
+
+
+def _cell(alg, method, hop=128, pct=20.0, **extra):
+    base = {"spectralSubtractor": dict(alpha=1.0, beta=0.05),
+            "wiener": dict(alpha=0.98, gain_floor=0.1),
+            "mmse": dict(alpha=0.98, ksi_min=0.01, gain_min=0.05, gain_max=1.0),
+            "omlsa": dict(alpha=0.9, ksi_min=0.01, gain_floor=0.1, noise_mu=0.95, q=0.4)}[alg]
+    return (0, alg, dict(base, n_fft=512, hop_length=hop, noise_percentile=pct,
+                         noise_method=method, **extra))
+
+
+def _layout(specs, L=8000, S=1):
+    (n_fft, items), = layout.specs_by_n_fft(S, L, specs, False, False)
+    return layout.PlanLayout(n_fft, S, L, items, False, False, False, cells_per_group=16)
+
+
+def test_noise_key_of_an_imcra_cell_beside_the_minstat_one():
+    T = 63
+    want = DEFAULT_VALUES[:3] + (1.2,) + DEFAULT_VALUES[4:]
+    for alg, (code, eps, _) in layout.ALGOS.items():
+        p = _cell(alg, "imcra", imcra_beta=1.2)[2]
+        method, slot, e, expand, mu, inverse = layout.noise_key(alg, p, T)
+        assert (method, slot, e, expand) == ("imcra", want, eps, False)
+        assert inverse == (code != "SS")
+        assert mu == {"SS": None, "WIENER": None, "MMSE": 0.98, "OMLSA": 0.95}[code]
+        assert not layout.key_is_static((method, slot, e, expand, mu, inverse))
+        # noise_percentile does not enter the key; the other trackers' names are not read
+        assert layout.noise_key(alg, dict(p, noise_percentile=3.0, mcra_delta=2.0, spp_ph_max=0.9,
+                                          minstat_av=1.0), T) == \
+            (method, slot, e, expand, mu, inverse)
+        # the algorithm's own alpha and beta are not the tracker's
+        assert slot[0] == 0.92
+        # beside the minstat cell: the same pipeline, another estimator slot
+        ms = layout.noise_key(alg, dict(p, noise_method="minstat"), T)
+        assert ms[0] == "minstat" and ms[1] == layout.minstat_values({})
+        for other in ("min_tracking", "mcra", "spp", "minstat"):
+            assert layout.noise_key(alg, dict(p, noise_method=other), T)[2:] == \
+                (e, expand, mu, inverse)
+        assert layout.noise_key(alg, p, 4) == \
+            layout.noise_key(alg, dict(p, noise_method="percentile"), 4)
+        assert layout.noise_key(alg, p, 4)[0] == "simple"
+
+
+def test_one_imcra_call_per_parameter_set_and_eps():
+    specs = [_cell("wiener", "imcra", 128, 10.0), _cell("wiener", "imcra", 128, 20.0),
+             _cell("spectralSubtractor", "imcra", 128), _cell("omlsa", "imcra", 128),
+             _cell("wiener", "imcra", 128, imcra_sub_frames=12, imcra_zeta0=1.5),
+             _cell("wiener", "imcra", 256), _cell("wiener", "min_tracking", 128),
+             _cell("wiener", "minstat", 128), _cell("wiener", "percentile", 256)]
+    lay = _layout(specs)
+    B = 257
+    other = DEFAULT_VALUES[:7] + (1.5, -18.0, 8, 12)
+    for hop, sets in ((128, [DEFAULT_VALUES, other]), (256, [DEFAULT_VALUES])):
+        calls = lay.noise_calls[hop]
+        names = [c[0] for c in calls]
+        T = 1 + 8000 // hop
+        assert names[-1] == "cse_noise_finish" and names.count("cse_noise_finish") == 1
+        assert names.count("cse_noise_minstat") == (1 if hop == 128 else 0)
+        sc = [c[1] for c in calls if c[0] == "cse_noise_imcra"]
+        assert len(sc) == len(sets)
+        for args, want in zip(sc, sets):
+            P, S, T_, B_, prm, eps, N = args
+            assert (P, S, T_, B_, eps) == (layout.Ref("P"), 1, T, B, 1e-10)
+            assert isinstance(prm, _lib.ImcraParams) and _as_tuple(prm) == want
+            assert N.buf == "raw" and lay.raw_off[(hop, "imcra", want, 1e-10)] == (N.off, T)
+            assert N.off + T * B <= lay.raw_elems
+    lay2 = _layout(specs + [_cell("mmse", "imcra", 128)])
+    sc = [c[1] for c in lay2.noise_calls[128] if c[0] == "cse_noise_imcra"]
+    assert sorted(a[5] for a in sc) == [1e-12, 1e-10, 1e-10]
+    # twins in noise_percentile share the estimate; the table is minstat's but for the call
+    a = _layout([_cell("wiener", "imcra", 128, 10.0), _cell("wiener", "imcra", 128, 20.0)])
+    m = _layout([_cell("wiener", "minstat", 128, 10.0), _cell("wiener", "minstat", 128, 20.0)])
+    assert len(a.raw_off) == 1 and a.cells.tobytes() == m.cells.tobytes()
+    assert [n for n, _ in a.noise_calls[128]] == ["cse_noise_imcra", "cse_noise_finish"]
+    with pytest.raises(ValueError, match="Unbekannte Methode: imcra2"):
+        _layout([_cell("wiener", "imcra2", 128)])
+
+
+def test_short_clip_takes_the_simple_estimate():
+    a = _layout([_cell("wiener", "imcra", 128)], L=300)
+    b = _layout([_cell("wiener", "percentile", 128)], L=300)
+    assert [c[0] for c in a.noise_calls[128]] == ["cse_noise_estimate", "cse_noise_finish"]
+    assert a.keys == b.keys and a.cells.tobytes() == b.cells.tobytes()
+
+
+def test_time_constants_at_other_frame_steps():
+    assert layout.imcra_time_constants(128, 16000) == layout.IMCRA_DEFAULTS
+    h = layout.imcra_time_constants(256, 16000)
+    assert set(h) == set(layout.IMCRA_DEFAULTS)
+    assert (h["sub_windows"], h["sub_frames"]) == (8, 8)
+    for k, tau in (("alpha", -0.008 / math.log(0.92)), ("alpha_s", -0.008 / math.log(0.9)),
+                   ("alpha_d", -0.008 / math.log(0.85))):
+        assert h[k] == pytest.approx(math.exp(-0.016 / tau), rel=1e-14)
+        assert h[k] == pytest.approx(layout.IMCRA_DEFAULTS[k] ** 2, rel=1e-14)
+    for k in ("beta", "b_min", "gamma0", "gamma1", "zeta0", "xi_min_db"):
+        assert h[k] == layout.IMCRA_DEFAULTS[k]
+    assert layout.imcra_time_constants(8000, 16000)["sub_frames"] == 1  # clipped
+    assert layout.imcra_time_constants(64, 16000)["sub_frames"] == 30
+    layout.imcra_values(h)  # a valid set
+    layout.imcra_values(layout.imcra_time_constants(64, 8000))
+    with pytest.raises(ValueError):
+        layout.imcra_time_constants(0, 16000)
+
+
+def test_grids_with_noise_methods_accepts_imcra():
+    methods = ("min_tracking", "minstat", "imcra")
+    grids = parameter_ranges.grids_with_noise_methods(methods)
+    for alg, g in grids.items():
+        assert g["noise_method"] == list(methods)
+        assert parameter_ranges.ALGORITHM_GRIDS[alg]["noise_method"] == ["percentile",
+                                                                         "min_tracking"]
+    assert "imcra" in parameter_ranges.grids_with_noise_methods.__doc__
+    specs = search.job_specs(1, grids=parameter_ranges.grids_with_noise_methods(("imcra",)))
+    for a, alg in enumerate(specs.algorithms):
+        rep = specs.grid_rep(a, 16000)
+        cells = specs.cells[alg]
+        assert len(set(rep.tolist())) == len(cells) // 2  # the noise_percentile twins
+        assert all(cells[r]["noise_method"] == "imcra" for r in rep)
