@@ -32,6 +32,10 @@ predictor of quality for this project's algorithm families), the same way: the
 clean side once per batch (cse_segsnr_prepare), then any number of cells
 (cse_segsnr_cells) with STOI's lag / clip test-signal definition.  The
 reference scores neither; evaluate_audio_quality adds them only on request.
+
+LpcPlan scores the two envelope-distortion measures of include/cse_lpc.h, the
+log-likelihood ratio and the LPC cepstrum distance (lower is better), through
+the same interface (cse_lpc_prepare / cse_lpc_cells).
 """
 
 import math
@@ -177,6 +181,16 @@ class SegSnrPlan:
     """Clean side of segSNR / fwSegSNR for S equal-length signals (clean:
     [S, L] f64 cuda) at 16 or 8 kHz."""
 
+    # the library's four entry points are _PREFIX + _workspace_bytes / _prepare /
+    # _scratch_bytes / _cells; _WHICH names the two score columns (LpcPlan
+    # scores through the same code with its own)
+    _PREFIX = "cse_segsnr"
+    _LABEL = "segSNR"
+    _WHICH = ("segsnr", "fwsegsnr")
+
+    def _fn(self, name):
+        return getattr(self.lib, f"{self._PREFIX}_{name}")
+
     def __init__(self, clean, sr=STOI_SR):
         if not _gpu_visible():
             raise _lib.CseError("no GPU visible: the HIP engine has no CPU fallback")
@@ -187,24 +201,25 @@ class SegSnrPlan:
         self.S, self.L = clean.shape
         self.clean = clean
         self.sr = int(sr)
-        nbytes = int(self.lib.cse_segsnr_workspace_bytes(self.S, self.L, self.sr))
+        nbytes = int(self._fn("workspace_bytes")(self.S, self.L, self.sr))
         if nbytes < 0:
-            raise NotImplementedError(f"segSNR: sample rate {sr} not supported (16000, 8000 Hz)")
+            raise NotImplementedError(
+                f"{self._LABEL}: sample rate {sr} not supported (16000, 8000 Hz)")
         self.ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=clean.device)
-        _lib.check(self.lib.cse_segsnr_prepare(_ptr(clean), self.S, self.L, self.sr, _ptr(self.ws),
-                                               _stream()), "cse_segsnr_prepare")
+        _lib.check(self._fn("prepare")(_ptr(clean), self.S, self.L, self.sr, _ptr(self.ws),
+                                       _stream()), f"{self._PREFIX}_prepare")
         self._scratch = None
 
     def cells_per_launch(self):
         """Cells of one launch: SEGSNR_SCRATCH_BYTES over the library's scratch
         per cell at this length and rate; SEGSNR_MAX_CELLS when it needs none."""
-        per = int(self.lib.cse_segsnr_scratch_bytes(1, self.L, self.sr))
+        per = int(self._fn("scratch_bytes")(1, self.L, self.sr))
         if per <= 0:
             return SEGSNR_MAX_CELLS
         return int(max(1, min(SEGSNR_MAX_CELLS, SEGSNR_SCRATCH_BYTES // per)))
 
     def _scratch_for(self, n):
-        nbytes = int(self.lib.cse_segsnr_scratch_bytes(n, self.L, self.sr))
+        nbytes = int(self._fn("scratch_bytes")(n, self.L, self.sr))
         if nbytes <= 0:
             return None
         if self._scratch is None or self._scratch.numel() < nbytes:
@@ -219,8 +234,9 @@ class SegSnrPlan:
         that score alone (the other column is NaN; "segsnr" skips the
         transforms)."""
         dev = self.clean.device
-        if which not in ("both", "segsnr", "fwsegsnr"):
-            raise ValueError(f"which={which!r}: 'both', 'segsnr' or 'fwsegsnr'")
+        first, second = self._WHICH
+        if which not in ("both", first, second):
+            raise ValueError(f"which={which!r}: 'both', {first!r} or {second!r}")
         if y.dtype != torch.float32 or not y.is_cuda:
             raise ValueError("y must be a float32 cuda tensor")
         if torch.is_tensor(y_offset):
@@ -268,12 +284,12 @@ class SegSnrPlan:
         for s in range(0, n, step):
             m = min(step, n - s)
             scratch = self._scratch_for(m)
-            _lib.check(self.lib.cse_segsnr_cells(
+            _lib.check(self._fn("cells")(
                 _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
                 self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
                 None if scratch is None else _ptr(scratch),
-                None if which == "fwsegsnr" else _ptr(cols[0, s:]),
-                None if which == "segsnr" else _ptr(cols[1, s:]), _stream()), "cse_segsnr_cells")
+                None if which == second else _ptr(cols[0, s:]),
+                None if which == first else _ptr(cols[1, s:]), _stream()), f"{self._PREFIX}_cells")
         out.copy_(cols.t())
         return out
 
@@ -283,19 +299,46 @@ class SegSnrPlan:
         return self.score_async(y, y_offset, sig_of, lag, clip, which=which).cpu().numpy()
 
 
-def _segsnr_pair(x, y, fs, which):
+class LpcPlan(SegSnrPlan):
+    """Clean side of the LLR / LPC cepstrum distance (include/cse_lpc.h) for S
+    equal-length signals at 16 or 8 kHz: SegSnrPlan's interface on
+    cse_lpc_prepare / cse_lpc_cells.  score_async returns [n, 2] (llr, cep);
+    which="llr" / "cep" computes that score alone (the other column is NaN;
+    "llr" skips the cepstrum recursion).  Clips of more than 1536 frames (11.5 s)
+    select through scratch the library sizes; the launches are chunked by it."""
+
+    _PREFIX = "cse_lpc"
+    _LABEL = "LLR/CEP"
+    _WHICH = ("llr", "cep")
+
+
+def _plan_pair(cls, x, y, fs, which):
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     if x.shape != y.shape:
         raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
     if x.ndim != 1 or x.size == 0:
-        raise ValueError("segsnr expects non-empty 1-D signals")
-    plan = SegSnrPlan(torch.as_tensor(x).cuda().view(1, -1), fs)
+        raise ValueError(f"{which} expects non-empty 1-D signals")
+    plan = cls(torch.as_tensor(x).cuda().view(1, -1), fs)
     yd = torch.as_tensor(y.astype(np.float32)).cuda()
-    v = float(plan.score(yd, [0], [0], clip=False, which=which)[0, 0 if which == "segsnr" else 1])
+    v = float(plan.score(yd, [0], [0], clip=False, which=which)[0, cls._WHICH.index(which)])
     if math.isnan(v):
         raise ValueError("no non-silent 30-ms frame")
     return v
+
+
+def _segsnr_pair(x, y, fs, which):
+    return _plan_pair(SegSnrPlan, x, y, fs, which)
+
+
+def llr(x, y, fs):
+    """Log-likelihood ratio (include/cse_lpc.h) of y against the clean x; lower is better."""
+    return _plan_pair(LpcPlan, x, y, fs, "llr")
+
+
+def cepstrum_distance(x, y, fs):
+    """LPC cepstrum distance (include/cse_lpc.h) of y against the clean x; lower is better."""
+    return _plan_pair(LpcPlan, x, y, fs, "cep")
 
 
 def segsnr(x, y, fs):
@@ -327,6 +370,16 @@ def calculate_segsnr(clean_reference, test_audio, sr):
 def calculate_fwsegsnr(clean_reference, test_audio, sr):
     """fwsegsnr with calculate_stoi's shape: trim to the common length, None on failure."""
     return _calculate_quality(fwsegsnr, "fwSegSNR", clean_reference, test_audio, sr)
+
+
+def calculate_llr(clean_reference, test_audio, sr):
+    """llr with calculate_stoi's shape: trim to the common length, None on failure."""
+    return _calculate_quality(llr, "LLR", clean_reference, test_audio, sr)
+
+
+def calculate_cep(clean_reference, test_audio, sr):
+    """cepstrum_distance with calculate_stoi's shape: trim to the common length, None on failure."""
+    return _calculate_quality(cepstrum_distance, "CEP", clean_reference, test_audio, sr)
 
 
 def stoi(x, y, fs_sig, extended=False):
@@ -396,9 +449,11 @@ def calculate_combined_speech_score(stoi_score, pesq_score):
 
 
 def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name="",
-                           quality=False):
+                           quality=False, distortion=False):
     """evaluation_metrics.evaluate_audio_quality (:61-101), same keys;
-    quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement)."""
+    quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement);
+    distortion=True adds llr_* and cep_* likewise, their improvement being
+    noisy - enhanced (lower is better)."""
     results = {}
     s_noisy = calculate_stoi(clean_reference, noisy_audio, sr)
     s_enh = calculate_stoi(clean_reference, enhanced_audio, sr)
@@ -423,6 +478,14 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
                 results[f"{key}_noisy"] = q_noisy
                 results[f"{key}_enhanced"] = q_enh
                 results[f"{key}_improvement"] = q_enh - q_noisy
+    if distortion:
+        for key, fn in (("llr", calculate_llr), ("cep", calculate_cep)):
+            d_noisy = fn(clean_reference, noisy_audio, sr)
+            d_enh = fn(clean_reference, enhanced_audio, sr)
+            if d_noisy is not None and d_enh is not None:
+                results[f"{key}_noisy"] = d_noisy
+                results[f"{key}_enhanced"] = d_enh
+                results[f"{key}_improvement"] = d_noisy - d_enh
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:
@@ -433,4 +496,7 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     for key, label in (("segsnr", "segSNR"), ("fwsegsnr", "fwSegSNR")):
         if f"{key}_noisy" in results:
             print(f"{label}: {results[key + '_noisy']:.2f} -> {results[key + '_enhanced']:.2f} dB")
+    for key, label in (("llr", "LLR"), ("cep", "CEP")):
+        if f"{key}_noisy" in results:
+            print(f"{label}: {results[key + '_noisy']:.3f} -> {results[key + '_enhanced']:.3f}")
     return results

@@ -25,7 +25,8 @@ A quality=True sweep (search.run_sweep) adds keys of its own in the same way:
 segsnr_noisy, fwsegsnr_noisy, and the fwSegSNR-optimal cell's fwsegsnr_best,
 best_params_fwsegsnr and snr_fwsegopt (their means in summary_means.json).  A
 row made without them has none of these keys, and the summary then has no such
-means.
+means.  A distortion=True sweep does the same with llr_noisy, cep_noisy and the
+LLR-optimal (lowest) cell's llr_best, best_params_llr and snr_llropt.
 """
 
 import json
@@ -59,6 +60,12 @@ QUALITY_SUMMARY_KEYS = (("segsnr_noisy_mean", "segsnr_noisy"),
                         ("snr_fwsegopt_mean", "snr_fwsegopt"))
 
 
+DISTORTION_ARGS = ("llr_noisy", "cep_noisy", "llr_best", "llr_params", "snr_llropt")
+DISTORTION_KEYS = ("llr_noisy", "cep_noisy", "llr_best", "best_params_llr", "snr_llropt")
+DISTORTION_SUMMARY_KEYS = (("llr_noisy_mean", "llr_noisy"), ("cep_noisy_mean", "cep_noisy"),
+                           ("llr_best_mean", "llr_best"), ("snr_llropt_mean", "snr_llropt"))
+
+
 def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
                stoi_best=None, stoi_params=None, snr_stoiopt=None, **quality):
     """One all_results.json row (run_algorithm_on_pair :314-338).  STOI
@@ -68,22 +75,29 @@ def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
     (:320-333: the balance objective needs PESQ).  The SNR-optimal cell goes
     to the extra keys snr_snropt / best_params_snr only.  The quality keywords
     (all or none: segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best, fwsegsnr_params,
-    snr_fwsegopt) add the QUALITY_KEYS of a quality=True sweep."""
+    snr_fwsegopt) add the QUALITY_KEYS of a quality=True sweep, the distortion
+    keywords (all or none: DISTORTION_ARGS) the DISTORTION_KEYS of a
+    distortion=True one."""
     row = {k: None for k in ROW_KEYS}
     row.update(alg=alg, stem=stem, sr=int(sr), snr_noisy=snr_noisy,
                best_params_stoi=dict(stoi_params or {}), best_params_pesq={},
                best_params_balanced={}, snr_snropt=best_snr,
                best_params_snr=dict(best_params or {}),
                stoi_noisy=stoi_noisy, stoi_stoiopt=stoi_best, snr_stoiopt=snr_stoiopt)
-    if quality:
-        unknown = set(quality) - set(QUALITY_ARGS)
-        if unknown:
-            raise TypeError(f"result_row: unexpected keywords {sorted(unknown)}")
+    unknown = set(quality) - set(QUALITY_ARGS) - set(DISTORTION_ARGS)
+    if unknown:
+        raise TypeError(f"result_row: unexpected keywords {sorted(unknown)}")
+    if set(quality) & set(QUALITY_ARGS):
         row.update(segsnr_noisy=quality.get("segsnr_noisy"),
                    fwsegsnr_noisy=quality.get("fwsegsnr_noisy"),
                    fwsegsnr_best=quality.get("fwsegsnr_best"),
                    best_params_fwsegsnr=dict(quality.get("fwsegsnr_params") or {}),
                    snr_fwsegopt=quality.get("snr_fwsegopt"))
+    if set(quality) & set(DISTORTION_ARGS):
+        row.update(llr_noisy=quality.get("llr_noisy"), cep_noisy=quality.get("cep_noisy"),
+                   llr_best=quality.get("llr_best"),
+                   best_params_llr=dict(quality.get("llr_params") or {}),
+                   snr_llropt=quality.get("snr_llropt"))
     return row
 
 
@@ -105,6 +119,9 @@ def summary_means(all_results, algorithms):
             entry[key] = safe_mean([r.get(field) for r in rows])
         if any("fwsegsnr_best" in r for r in rows):  # a quality=True sweep
             for key, field in QUALITY_SUMMARY_KEYS:
+                entry[key] = safe_mean([r.get(field) for r in rows])
+        if any("llr_best" in r for r in rows):  # a distortion=True sweep
+            for key, field in DISTORTION_SUMMARY_KEYS:
                 entry[key] = safe_mean([r.get(field) for r in rows])
         out[alg] = entry
     return out

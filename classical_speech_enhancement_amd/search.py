@@ -45,6 +45,13 @@ frequency-weighted segmental SNR (cse_segsnr_cells, include/cse_segsnr.h;
 Hu & Loizou 2008) of the same finalised waveforms, as two more table columns
 (QUALITY_COLUMNS) with objectives "segsnr" and "fwsegsnr".  The default leaves
 every table, record and result as it was.
+
+distortion=True (the same four functions) adds the two LPC envelope measures
+of include/cse_lpc.h, the log-likelihood ratio and the cepstrum distance
+(cse_lpc_cells; Hu & Loizou 2008's best predictor of signal distortion), as
+columns 8 and 9 (DISTORTION_COLUMNS) of a table that then always has NCOL + 4
+columns: columns 6 and 7 are the quality columns, NaN unless quality=True is
+given too.  "llr" and "cep" are objectives that are minimised.
 """
 
 import math
@@ -59,8 +66,9 @@ from .parameter_ranges import ALGORITHM_GRIDS, grid_cells
 ALGO_WEIGHT = {"spectralSubtractor": 1.0, "wiener": 1.1, "mmse": 2.0, "omlsa": 3.0}
 # tolerance of the best-so-far update per objective (speech_enhancement_comparison.py:183,194,205)
 # segsnr / fwsegsnr (dB): the reference's step for PESQ, the quality objective they stand in for
+# llr / cep: that PESQ step of 1e-3 on a 5-wide scale carried to a 2-wide and a 10-wide one
 TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5,
-             "segsnr": 1e-3, "fwsegsnr": 1e-3}
+             "segsnr": 1e-3, "fwsegsnr": 1e-3, "llr": 1e-4, "cep": 1e-3}
 
 # one float64 row per cell.  lag: finalize_enhanced's alignment lag (0 when
 # not aligned); xstatus: cse_xcorr_lag's status (engine: XCORR_OK, XCORR_FLAT =
@@ -73,7 +81,16 @@ NCOL = len(RECORD_FIELDS) - 1
 QUALITY_COLUMNS = {"segsnr": 6, "fwsegsnr": 7}
 # where select_best's scan starts: the reference's -1 (speech_enhancement_comparison.py:126-141)
 # unless the objective's values go below it (dB scores clamped to [-10, 35])
-SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf}
+SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf, "llr": -math.inf, "cep": -math.inf}
+# distortion=True tables have NCOL + 4 columns: the two quality columns (NaN
+# without quality=True), then these.  Lower is better: select_best scans the
+# negated column
+DISTORTION_COLUMNS = {"llr": 8, "cep": 9}
+
+
+def table_width(quality=False, distortion=False):
+    """Columns of a table: NCOL, + 2 with quality, + 4 with distortion (either way)."""
+    return NCOL + (4 if distortion else 2 if quality else 0)
 # bound on the cell waveforms held at once for STOI scoring (f32 bytes): 48 GiB
 # of the 288 GB HBM, i.e. 10 full 10-s pairs (7,308 computed cells x 640 KB each)
 # per batch, two batches in flight.  100-pair sweep (late r04, call_r04s.sh in profiles/r04_commands.md):
@@ -286,14 +303,17 @@ def _unique_inverse(x):
     return np.flatnonzero(mark), rank[x]
 
 
-def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True, quality=False):
+def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True, quality=False,
+                   distortion=False):
     """Device compute of the cells ``ids``: per-cell (sse, snr, finite, stoi,
     lag, xstatus), scored after finalize_enhanced's alignment (align=False: at
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
     waveforms are kept); stoi="extended" fills it with extended STOI.
     quality=True appends segsnr and fwsegsnr (QUALITY_COLUMNS; NaN where the
     cell is not finite), scored on the side stream from the same waveforms,
-    with or without STOI.
+    with or without STOI.  distortion=True makes the rows NCOL + 4 wide and
+    fills llr and cep (DISTORTION_COLUMNS) the same way; the quality columns
+    are then there too, NaN unless quality=True.
 
     clean/noisy: lists of 1-D float arrays (host) indexed by pair.  Pairs are
     batched by length (the engine's signal batches are rectangular), and, when
@@ -316,7 +336,8 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     eng = engine or Engine()
     size0 = eng.plan_cache_size
     try:
-        return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, bool(quality))
+        return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, bool(quality),
+                               bool(distortion))
     finally:
         if own:
             eng._plan_cache.clear()
@@ -326,11 +347,11 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
                 eng._plan_cache.popitem(last=False)
 
 
-def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False):
+def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, distortion=False):
     import torch
     from .engine import snr_db, spec_fingerprint, structure_digest
-    from .metrics import SegSnrPlan, StoiPlan
-    keep = bool(stoi) or quality  # the cell waveforms are scored on the side stream
+    from .metrics import LpcPlan, SegSnrPlan, StoiPlan
+    keep = bool(stoi) or quality or distortion  # the cell waveforms are scored on the side stream
     ids = np.asarray(ids, dtype=np.int64)
     lengths = [len(x) for x in noisy]
     js_specs = isinstance(specs, JobSpecs)
@@ -340,7 +361,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False):
     else:
         comp, back = ids, np.arange(len(ids))
         pair_of = np.fromiter((specs[c][0] for c in comp), dtype=np.int64, count=len(comp))
-    vals = np.full((len(comp), NCOL + (2 if quality else 0)), np.nan)
+    vals = np.full((len(comp), table_width(quality, distortion)), np.nan)
     by_len = OrderedDict()
     upairs, first = np.unique(pair_of, return_index=True)
     for pair in upairs[np.argsort(first, kind="stable")].tolist():  # first-appearance order
@@ -358,13 +379,14 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False):
     nbatch = 0
 
     def collect(item):
-        rows_, fin_, out_, qout_, ev_, _refs = item
+        rows_, fin_, out_, qout_, dout_, ev_, _refs = item
         ev_.synchronize()
         if out_ is not None:
             vals[rows_, 3] = np.where(fin_, out_.cpu().numpy(), np.nan)
-        if qout_ is not None:
-            vals[rows_, NCOL:] = np.where(np.asarray(fin_, dtype=bool)[:, None],
-                                          qout_.cpu().numpy(), np.nan)
+        for first, pair_ in ((NCOL, qout_), (NCOL + 2, dout_)):
+            if pair_ is not None:
+                vals[rows_, first:first + 2] = np.where(np.asarray(fin_, dtype=bool)[:, None],
+                                                        pair_.cpu().numpy(), np.nan)
 
     sorted_pairs = len(pair_of) < 2 or bool((pair_of[1:] >= pair_of[:-1]).all())
     for L, pairs_l in by_len.items():
@@ -395,10 +417,11 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False):
                                           np.asarray(clean[p], np.float64))) for p in pairs])
             splan = StoiPlan(cl, extended=(stoi == "extended")) if stoi else None
             qplan = SegSnrPlan(cl) if quality else None
+            dplan = LpcPlan(cl) if distortion else None
             state = {}
 
             def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, qplan=qplan,
-                        state=state):
+                        dplan=dplan, state=state):
                 """one n_fft's cells are final: queue their scores on the side stream"""
                 idx = np.asarray(p.idx, dtype=np.int64)
                 lg = lag if lag is not None else np.zeros(len(idx), dtype=np.int64)
@@ -409,17 +432,19 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False):
                 lag_d = torch.as_tensor(np.asarray(lg, dtype=np.int32)).cuda()
                 y = p.y_all.view(-1)  # the run's waveform buffer (every n_fft's rows)
                 side.wait_stream(main)
-                out = qout = None
+                out = qout = dout = None
                 with torch.cuda.stream(side):
                     if splan is not None:
                         out = splan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     if qplan is not None:
                         qout = qplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
+                    if dplan is not None:
+                        dout = dplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 state["ev"] = ev
-                inflight.append((js[idx], fin, out, qout, ev,
-                                 (y, off_d, sig_d, lag_d, splan, qplan)))
+                inflight.append((js[idx], fin, out, qout, dout, ev,
+                                 (y, off_d, sig_d, lag_d, splan, qplan, dplan)))
                 while len(inflight) > 2:  # bound the STOI scratch held in flight
                     collect(inflight.pop(0))
 
@@ -520,14 +545,15 @@ def _scan_records(sc, rec, ids, tol, start=-1.0):
     return win, (incumbent if win >= 0 else None)
 
 
-def _select_best_blocks(specs, table, col, tol, start=-1.0):
+def _select_best_blocks(specs, table, col, tol, start=-1.0, sign=1.0):
     """select_best over a JobSpecs table: each algorithm's cells of all pairs
     as one [pairs, grid] block (the columns of a (pair, algorithm) run are
-    contiguous), running maxima along the grid axis in one call."""
+    contiguous), running maxima along the grid axis in one call.  sign = -1:
+    the scan runs on the negated column (the scores returned are negated too)."""
     n_pairs = len(specs) // max(specs.per_pair, 1)
     # the score column with skipped cells at -inf (a finite cell whose score
     # is not NaN), as [pairs, cells of one pair]
-    sc_all = np.asarray(table[:n_pairs * specs.per_pair, col], dtype=np.float64)
+    sc_all = sign * np.asarray(table[:n_pairs * specs.per_pair, col], dtype=np.float64)
     ok = (table[:n_pairs * specs.per_pair, 2] != 0) & (sc_all == sc_all)
     sc_all = np.where(ok, sc_all, -np.inf).reshape(n_pairs, specs.per_pair)
     found = {}
@@ -563,20 +589,37 @@ def select_best(specs, table, objective="snr", tol=None):
     "segsnr" / "fwsegsnr" (a quality=True table): the same scan with their
     tolerance, started below every score (SCAN_START): the reference's -1 is a
     floor for scores that are never negative, and these are dB values clamped
-    to [-10, 35], so the first scored cell is always taken."""
+    to [-10, 35], so the first scored cell is always taken.
+
+    "llr" / "cep" (a distortion=True table) are minimised: the same scan runs
+    on the negated column, started at -inf, so a cell replaces the incumbent
+    when its value < incumbent - tol; the score returned is the value itself."""
+    best = _select_best(specs, table, objective, tol)
+    if objective in DISTORTION_COLUMNS:  # -(-v) is v, bit for bit
+        best = OrderedDict((k, (win, None if sc is None else -sc)) for k, (win, sc) in best.items())
+    return best
+
+
+def _select_best(specs, table, objective, tol):
     tol = TOLERANCE[objective] if tol is None else tol
+    sign = 1.0
     if objective in QUALITY_COLUMNS:
         col = QUALITY_COLUMNS[objective]
         if np.ndim(table) != 2 or np.shape(table)[1] <= col:
             raise ValueError(f"objective {objective!r} needs a quality=True table of "
                              f"{NCOL + 2} columns, this one has {np.shape(table)[-1]}")
+    elif objective in DISTORTION_COLUMNS:
+        col, sign = DISTORTION_COLUMNS[objective], -1.0
+        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
+            raise ValueError(f"objective {objective!r} needs a distortion=True table of "
+                             f"{NCOL + 4} columns, this one has {np.shape(table)[-1]}")
     elif objective in ("snr", "stoi"):
         col = TABLE_COLUMN[objective]
     else:
         raise ValueError(f"objective {objective!r} is not scored on the device (pesq is absent)")
     scan_start = SCAN_START.get(objective, -1.0)
     if isinstance(specs, JobSpecs) and tol >= 0.0:
-        return _select_best_blocks(specs, table, col, tol, scan_start)
+        return _select_best_blocks(specs, table, col, tol, scan_start, sign)
     groups = OrderedDict()
     if isinstance(specs, JobSpecs):  # (pair, algorithm) runs are contiguous
         per = [len(specs.cells[a]) for a in specs.algorithms]
@@ -591,7 +634,7 @@ def select_best(specs, table, objective="snr", tol=None):
     best = OrderedDict()
     for key, ids in groups.items():
         ids = np.asarray(ids, dtype=np.int64)
-        sc = table[ids, col]
+        sc = sign * table[ids, col]
         ok = (table[ids, 2] != 0) & (sc == sc)  # finite cell, score not NaN
         sc = np.where(ok, sc, -np.inf)
         incumbent, win = scan_start, -1
@@ -617,7 +660,7 @@ def select_best(specs, table, objective="snr", tol=None):
 
 
 def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
-             extended=False, quality=False):
+             extended=False, quality=False, distortion=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
@@ -626,7 +669,9 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     compute (engine_compute) scores extended STOI into the stoi column; a
     compute function given by the caller scores what it scores.  quality=True:
     the table has NCOL + 2 columns (QUALITY_COLUMNS: segsnr, fwsegsnr), filled
-    by the default compute; a caller's compute function returns them itself."""
+    by the default compute; a caller's compute function returns them itself.
+    distortion=True: NCOL + 4 columns (the quality columns, NaN without
+    quality=True, then DISTORTION_COLUMNS: llr, cep), likewise."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
@@ -634,16 +679,18 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     lengths = [len(x) for x in noisy]
     rank_of, _ = assign_shards(specs, lengths, world)
     ids = np.nonzero(rank_of == rank)[0]
-    ncol = NCOL + (2 if quality else 0)
-    if compute is None and (extended or quality):
+    ncol = table_width(quality, distortion)
+    if compute is None and (extended or quality or distortion):
         def compute(clean, noisy, specs, ids):
             return engine_compute(clean, noisy, specs, ids,
-                                  stoi="extended" if extended else True, quality=quality)
+                                  stoi="extended" if extended else True, quality=quality,
+                                  distortion=distortion)
     compute = compute or engine_compute
     vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, ncol))
     if np.ndim(vals) != 2 or np.shape(vals)[1] != ncol:
         raise ValueError(f"compute returned rows of shape {np.shape(vals)}, expected "
-                         f"{ncol} columns (quality={bool(quality)})")
+                         f"{ncol} columns (quality={bool(quality)}"
+                         + (", distortion=True)" if distortion else ")"))
     if not dist_on and len(ids) == len(specs):  # one process, every cell in order: no gather
         table = np.asarray(vals, dtype=np.float64)
     else:
@@ -669,13 +716,19 @@ def _device_quality(clean, test, sr):
     return calculate_segsnr(clean, test, sr), calculate_fwsegsnr(clean, test, sr)
 
 
+def _device_distortion(clean, test, sr):
+    """(llr, cep) of test against clean on the device, None for a failure."""
+    from .metrics import calculate_cep, calculate_llr
+    return calculate_llr(clean, test, sr), calculate_cep(clean, test, sr)
+
+
 def _opt(v):
     return None if v != v else float(v)
 
 
 def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_ranges=None,
                         compute=None, stoi_fn=None, extended=False, quality=False,
-                        quality_fn=None):
+                        quality_fn=None, distortion=False, distortion_fn=None):
     """Single-pair, single-algorithm mirror of the reference's
     optimize_parameters (speech_enhancement_comparison.py:109-252), scored by
     STOI and SNR: returns {'stoi': {'score', 'params', 'cell', 'snr'},
@@ -690,7 +743,10 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     'segsnr' and 'fwsegsnr' entries shaped like 'stoi' ({'score', 'params',
     'cell', 'snr'}, None when no cell has the score), with their baselines
     (quality_fn(clean, noisy, sr) -> (segsnr, fwsegsnr); default: the device)
-    and improvements."""
+    and improvements.
+    distortion=True: likewise 'llr' and 'cep' entries from the two distortion
+    columns (distortion_fn(clean, noisy, sr) -> (llr, cep) for the baselines);
+    both are minimised, so their improvement is baseline - score."""
     from .engine import canonical_algo
     if sr != 16000:
         raise ValueError("the device path runs at 16 kHz (prepare_pair resamples to 16 kHz)")
@@ -700,7 +756,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     clean = [np.asarray(clean_reference, np.float64)]
     noisy = [np.asarray(noisy_audio, np.float64)]
     table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended,
-                           quality=quality)
+                           quality=quality, distortion=distortion)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -734,11 +790,24 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
                          "snr": float(table[qid, 1])}
             out["baseline"][name] = base_q[k] or 0
             out["improvements"][name] = qscore - out["baseline"][name]
+    if distortion:
+        base_d = None
+        for k, name in enumerate(("llr", "cep")):
+            out[name] = None
+            did, dscore = select_best(specs, table, name)[(0, alg)]
+            if did < 0:
+                continue
+            if base_d is None:
+                base_d = (distortion_fn or _device_distortion)(clean[0], noisy[0], sr)
+            out[name] = {"score": dscore, "params": dict(specs[did][2]), "cell": int(did),
+                         "snr": float(table[did, 1])}
+            out["baseline"][name] = base_d[k] or 0
+            out["improvements"][name] = out["baseline"][name] - dscore
     return out
 
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
-              group=None, device=None, extended=False, quality=False):
+              group=None, device=None, extended=False, quality=False, distortion=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
@@ -753,22 +822,28 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     fwSegSNR-best cell's waveform is written as ..._optimized_fwsegsnr.wav and
     each row gains segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best,
     best_params_fwsegsnr and snr_fwsegopt (means in summary_means.json).  The
-    segSNR winner is select_best(specs, table, "segsnr")'s."""
+    segSNR winner is select_best(specs, table, "segsnr")'s.
+    distortion=True: the cells are also scored by the LLR and the cepstrum
+    distance; the LLR-best (lowest) cell's waveform is written as
+    ..._optimized_llr.wav and each row gains llr_noisy, cep_noisy, llr_best,
+    best_params_llr and snr_llropt (means in summary_means.json).  The CEP
+    winner is select_best(specs, table, "cep")'s."""
     import torch
     import torch.distributed as dist
     from . import results
     from .engine import Engine
-    from .metrics import SegSnrPlan, StoiPlan
+    from .metrics import LpcPlan, SegSnrPlan, StoiPlan
     grids = grids or ALGORITHM_GRIDS
     algorithms = list(algorithms or grids)
     specs = job_specs(len(noisy), algorithms, grids)
     table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
-                           quality=quality)
+                           quality=quality, distortion=distortion)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
     best_stoi = select_best(specs, table, "stoi")
     best_fw = select_best(specs, table, "fwsegsnr") if quality else None
+    best_llr = select_best(specs, table, "llr") if distortion else None
     eng = Engine()
     rows = []
     for pair, stem in enumerate(stems):
@@ -783,6 +858,10 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         if quality:
             qplan = SegSnrPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
             q_noisy = [_opt(v) for v in qplan.score(nf, [0], [0], clip=False)[0]]
+        d_noisy = None
+        if distortion:
+            dplan = LpcPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
+            d_noisy = [_opt(v) for v in dplan.score(nf, [0], [0], clip=False)[0]]
         x = torch.as_tensor(n).cuda().view(1, -1)
         cl = torch.as_tensor(c).cuda().view(1, -1)
         for alg in algorithms:
@@ -793,7 +872,8 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
             out_dir = os.path.join(out_root, f"results_{alg}")
             os.makedirs(out_dir, exist_ok=True)
             fid, fscore = best_fw[(pair, alg)] if quality else (-1, None)
-            for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid)):
+            lid, lscore = best_llr[(pair, alg)] if distortion else (-1, None)
+            for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid), ("llr", lid)):
                 if k < 0:
                     continue
                 res = eng.run(x, [(0, alg, specs[k][2])], clean=cl, want_waveforms=True, align=True)
@@ -810,7 +890,12 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                     segsnr_noisy=q_noisy[0], fwsegsnr_noisy=q_noisy[1],
                     fwsegsnr_best=None if fid < 0 else float(fscore),
                     fwsegsnr_params=None if fid < 0 else specs[fid][2],
-                    snr_fwsegopt=None if fid < 0 else float(table[fid, 1])))))
+                    snr_fwsegopt=None if fid < 0 else float(table[fid, 1]))),
+                **({} if not distortion else dict(
+                    llr_noisy=d_noisy[0], cep_noisy=d_noisy[1],
+                    llr_best=None if lid < 0 else float(lscore),
+                    llr_params=None if lid < 0 else specs[lid][2],
+                    snr_llropt=None if lid < 0 else float(table[lid, 1])))))
             if extended:
                 rows[-1]["stoi_extended"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
