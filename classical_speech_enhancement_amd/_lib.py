@@ -1,7 +1,7 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
-include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h and
-include/cse_lpc.h).
+include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h
+and include/cse_sisdr.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -125,6 +125,9 @@ EXPORTS_IMCRA = ("cse_imcra_default_params", "cse_noise_imcra")
 # include/cse_lpc.h (log-likelihood ratio and LPC cepstrum distance), likewise
 EXPORTS_LPC = ("cse_lpc_workspace_bytes", "cse_lpc_prepare", "cse_lpc_scratch_bytes",
                "cse_lpc_cells")
+# include/cse_sisdr.h (SI-SDR, SI-SIR and SI-SAR), likewise
+EXPORTS_SISDR = ("cse_sisdr_workspace_bytes", "cse_sisdr_prepare", "cse_sisdr_scratch_bytes",
+                 "cse_sisdr_cells")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -246,6 +249,14 @@ def load(path=LIB_PATH):
     lib.cse_lpc_scratch_bytes.argtypes = [i64, i64, i32]
     lib.cse_lpc_cells.restype = i32
     lib.cse_lpc_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P, P]
+    lib.cse_sisdr_workspace_bytes.restype = i64
+    lib.cse_sisdr_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cse_sisdr_prepare.restype = i32
+    lib.cse_sisdr_prepare.argtypes = [P, P, i64, i64, i32, P, P]
+    lib.cse_sisdr_scratch_bytes.restype = i64
+    lib.cse_sisdr_scratch_bytes.argtypes = [i64, i64]
+    lib.cse_sisdr_cells.restype = i32
+    lib.cse_sisdr_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, P, P, P, P, P, P, P]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

@@ -36,6 +36,11 @@ reference scores neither; evaluate_audio_quality adds them only on request.
 LpcPlan scores the two envelope-distortion measures of include/cse_lpc.h, the
 log-likelihood ratio and the LPC cepstrum distance (lower is better), through
 the same interface (cse_lpc_prepare / cse_lpc_cells).
+
+SiSdrPlan scores the scale-invariant SDR of include/cse_sisdr.h (Le Roux et al.
+2019) and, when the batch's noisy signals are given, its split into SI-SIR
+(residual interference) and SI-SAR (artifacts) through cse_sisdr_prepare /
+cse_sisdr_cells, with the same lag / clip test-signal definition, at any rate.
 """
 
 import math
@@ -312,6 +317,143 @@ class LpcPlan(SegSnrPlan):
     _WHICH = ("llr", "cep")
 
 
+class SiSdrPlan:
+    """Clean side of SI-SDR / SI-SIR / SI-SAR (include/cse_sisdr.h) for S
+    equal-length signals (clean: [S, L] f64 cuda, any rate).  noisy ([S, L] f64
+    cuda) gives the interference noisy - clean; without it only SI-SDR is
+    defined.  zero_mean removes the means of the signals first (the sums are
+    centred)."""
+
+    _WHICH = ("sisdr", "sisir", "sisar")
+
+    def __init__(self, clean, noisy=None, zero_mean=True):
+        if not _gpu_visible():
+            raise _lib.CseError("no GPU visible: the HIP engine has no CPU fallback")
+        self.lib = _lib.load()
+        clean = clean.contiguous()
+        if clean.dtype != torch.float64 or clean.dim() != 2 or not clean.is_cuda:
+            raise ValueError("clean must be a [S, L] float64 cuda tensor")
+        if noisy is not None:
+            noisy = noisy.contiguous()
+            if noisy.dtype != torch.float64 or noisy.shape != clean.shape or \
+                    noisy.device != clean.device:
+                raise ValueError("noisy must be a float64 cuda tensor of clean's shape and device")
+        self.S, self.L = clean.shape
+        if self.L < 1:
+            raise ValueError("SI-SDR expects non-empty signals")
+        self.clean = clean
+        self.with_noise = noisy is not None
+        self.zero_mean = bool(zero_mean)
+        nbytes = int(self.lib.cse_sisdr_workspace_bytes(self.S, self.L, int(self.with_noise)))
+        self.ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=clean.device)
+        _lib.check(self.lib.cse_sisdr_prepare(
+            _ptr(clean), None if noisy is None else _ptr(noisy), self.S, self.L,
+            int(self.zero_mean), _ptr(self.ws), _stream()), "cse_sisdr_prepare")
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True, out=None, which="all"):
+        """Enqueue the scores of every cell; returns the [n, 3] f64 cuda result
+        (sisdr, sisir, sisar).  The arguments are StoiPlan.score_async's: host
+        index arrays are validated and uploaded, cuda tensors (int64 / int32 /
+        int32) are taken as they are.  which="sisdr" computes SI-SDR alone
+        (the other columns are NaN; the interference is not read); a plan made
+        without noisy scores nothing else."""
+        dev = self.clean.device
+        if which not in ("all", "sisdr"):
+            raise ValueError(f"which={which!r}: 'all' or 'sisdr'")
+        if y.dtype != torch.float32 or not y.is_cuda:
+            raise ValueError("y must be a float32 cuda tensor")
+        if torch.is_tensor(y_offset):
+            off, sig = y_offset, sig_of
+            if not torch.is_tensor(sig):
+                raise ValueError("sig_of must be a cuda tensor when y_offset is one")
+            if off.dtype != torch.int64 or sig.dtype != torch.int32:
+                raise ValueError("device y_offset / sig_of must be int64 / int32")
+            if off.device != dev or sig.device != dev:
+                raise ValueError("device y_offset / sig_of must live on the clean signal's GPU")
+            if not (off.is_contiguous() and sig.is_contiguous()):
+                raise ValueError("device y_offset / sig_of must be contiguous")
+            n = int(off.numel())
+            if int(sig.numel()) != n:
+                raise ValueError("y_offset and sig_of differ in length")
+        else:
+            off_h = np.asarray(y_offset, dtype=np.int64)
+            sig_h = np.asarray(sig_of, dtype=np.int32)
+            n = len(off_h)
+            if len(sig_h) != n:
+                raise ValueError("y_offset and sig_of differ in length")
+            if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= self.S):
+                raise ValueError("sig_of out of range")
+            if n and (int(off_h.min()) < 0 or int(off_h.max()) + self.L > y.numel()):
+                raise ValueError("a cell's output runs past the end of y")
+            off = torch.as_tensor(off_h, device=dev)
+            sig = torch.as_tensor(sig_h, device=dev)
+        lg = None
+        if lag is not None:
+            if torch.is_tensor(lag):
+                if lag.device != dev:
+                    raise ValueError("device lag must live on the clean signal's GPU")
+                lg = lag.to(torch.int32).contiguous()
+            else:
+                lg = torch.as_tensor(np.asarray(lag, dtype=np.int32), device=dev)
+            if int(lg.numel()) != n:
+                raise ValueError("lag and y_offset differ in length")
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        if out.shape != (n, 3) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n, 3] float64 tensor")
+        # the library writes one column each: planar rows, then one copy
+        cols = torch.full((3, n), float("nan"), dtype=torch.float64, device=dev)
+        parts = which == "all" and self.with_noise
+        for s in range(0, n, SEGSNR_MAX_CELLS):
+            m = min(SEGSNR_MAX_CELLS, n - s)
+            _lib.check(self.lib.cse_sisdr_cells(
+                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
+                self.S, self.L, 1 if clip else 0, _ptr(self.clean), _ptr(self.ws), None,
+                _ptr(cols[0, s:]), _ptr(cols[1, s:]) if parts else None,
+                _ptr(cols[2, s:]) if parts else None, _stream()), "cse_sisdr_cells")
+        out.copy_(cols.t())
+        return out
+
+    def score(self, y, y_offset, sig_of, lag=None, clip=True, which="all"):
+        """score_async, synchronised: [n, 3] numpy (sisdr, sisir, sisar); NaN,
+        +inf and -inf as include/cse_sisdr.h's IEEE rules give them."""
+        return self.score_async(y, y_offset, sig_of, lag, clip, which=which).cpu().numpy()
+
+
+def si_sdr(x, y, noisy=None, zero_mean=True):
+    """SI-SDR in dB (include/cse_sisdr.h) of y against the clean x; with noisy
+    (the unprocessed input, x plus the interference) the triple (si_sdr, si_sir,
+    si_sar).  Values may be +-inf or NaN as the header's IEEE rules give them."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.shape != y.shape:
+        raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
+    if x.ndim != 1 or x.size == 0:
+        raise ValueError("si_sdr expects non-empty 1-D signals")
+    nz = None
+    if noisy is not None:
+        nz = np.asarray(noisy, dtype=np.float64)
+        if nz.shape != x.shape:
+            raise Exception(f"x and noisy should have the same length, found {x.shape} and "
+                            f"{nz.shape}")
+        nz = torch.as_tensor(nz).cuda().view(1, -1)
+    plan = SiSdrPlan(torch.as_tensor(x).cuda().view(1, -1), nz, zero_mean=zero_mean)
+    yd = torch.as_tensor(y.astype(np.float32)).cuda()
+    v = plan.score(yd, [0], [0], clip=False)[0]
+    return float(v[0]) if noisy is None else (float(v[0]), float(v[1]), float(v[2]))
+
+
+def calculate_sisdr(clean_reference, test_audio, sr):
+    """si_sdr with calculate_stoi's shape: trim to the common length, None on
+    failure (a NaN score included).  sr is not used: the score has no rate."""
+    def fn(x, y, _sr):
+        v = si_sdr(x, y)
+        if math.isnan(v):
+            raise ValueError("SI-SDR is undefined (an all-zero signal)")
+        return v
+    return _calculate_quality(fn, "SI-SDR", clean_reference, test_audio, sr)
+
+
 def _plan_pair(cls, x, y, fs, which):
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
@@ -448,12 +590,31 @@ def calculate_combined_speech_score(stoi_score, pesq_score):
     return 0.5 * stoi_score + 0.5 * (max(0, pesq_score) / 4.5)
 
 
+def _separation(clean_reference, noisy_audio, enhanced_audio):
+    """sisdr_enhanced, sisir_enhanced and sisar_enhanced, and sisdr_noisy with
+    sisdr_improvement (the noisy input's SI-SAR carries no meaning:
+    include/cse_sisdr.h); {} on failure."""
+    try:
+        n = min(len(clean_reference), len(noisy_audio), len(enhanced_audio))
+        c, z = np.asarray(clean_reference)[:n], np.asarray(noisy_audio)[:n]
+        sdr, sir, sar = si_sdr(c, np.asarray(enhanced_audio)[:n], noisy=z)
+        base = si_sdr(c, z)
+        return {"sisdr_noisy": base, "sisdr_enhanced": sdr, "sisdr_improvement": sdr - base,
+                "sisir_enhanced": sir, "sisar_enhanced": sar}
+    except (NotImplementedError, _lib.CseError):
+        raise  # no device / unsupported: not a score failure
+    except Exception as e:  # calculate_stoi's catch-all
+        print(f"SI-SDR calculation failed: {e}")
+        return {}
+
+
 def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name="",
-                           quality=False, distortion=False):
+                           quality=False, distortion=False, separation=False):
     """evaluation_metrics.evaluate_audio_quality (:61-101), same keys;
     quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement);
     distortion=True adds llr_* and cep_* likewise, their improvement being
-    noisy - enhanced (lower is better)."""
+    noisy - enhanced (lower is better); separation=True adds sisdr_enhanced,
+    sisir_enhanced and sisar_enhanced, and sisdr_noisy with sisdr_improvement."""
     results = {}
     s_noisy = calculate_stoi(clean_reference, noisy_audio, sr)
     s_enh = calculate_stoi(clean_reference, enhanced_audio, sr)
@@ -486,6 +647,8 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
                 results[f"{key}_noisy"] = d_noisy
                 results[f"{key}_enhanced"] = d_enh
                 results[f"{key}_improvement"] = d_noisy - d_enh
+    if separation:
+        results.update(_separation(clean_reference, noisy_audio, enhanced_audio))
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:
@@ -499,4 +662,7 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     for key, label in (("llr", "LLR"), ("cep", "CEP")):
         if f"{key}_noisy" in results:
             print(f"{label}: {results[key + '_noisy']:.3f} -> {results[key + '_enhanced']:.3f}")
+    if "sisdr_enhanced" in results:
+        print(f"SI-SDR: {results['sisdr_noisy']:.2f} -> {results['sisdr_enhanced']:.2f} dB "
+              f"(SI-SIR {results['sisir_enhanced']:.2f}, SI-SAR {results['sisar_enhanced']:.2f})")
     return results

@@ -26,7 +26,12 @@ segsnr_noisy, fwsegsnr_noisy, and the fwSegSNR-optimal cell's fwsegsnr_best,
 best_params_fwsegsnr and snr_fwsegopt (their means in summary_means.json).  A
 row made without them has none of these keys, and the summary then has no such
 means.  A distortion=True sweep does the same with llr_noisy, cep_noisy and the
-LLR-optimal (lowest) cell's llr_best, best_params_llr and snr_llropt.
+LLR-optimal (lowest) cell's llr_best, best_params_llr and snr_llropt.  A
+separation=True sweep does the same with sisdr_noisy and the SI-SDR-optimal
+cell's sisdr_best, sisir_sisdropt, sisar_sisdropt (the interference and artifact
+parts of its error), best_params_sisdr and snr_sisdropt.  There is no
+sisar_noisy: the unprocessed input's SI-SAR carries no meaning
+(include/cse_sisdr.h).
 """
 
 import json
@@ -66,6 +71,16 @@ DISTORTION_SUMMARY_KEYS = (("llr_noisy_mean", "llr_noisy"), ("cep_noisy_mean", "
                            ("llr_best_mean", "llr_best"), ("snr_llropt_mean", "snr_llropt"))
 
 
+SEPARATION_ARGS = ("sisdr_noisy", "sisdr_best", "sisir_sisdropt", "sisar_sisdropt",
+                   "sisdr_params", "snr_sisdropt")
+SEPARATION_KEYS = ("sisdr_noisy", "sisdr_best", "sisir_sisdropt", "sisar_sisdropt",
+                   "best_params_sisdr", "snr_sisdropt")
+SEPARATION_SUMMARY_KEYS = (("sisdr_noisy_mean", "sisdr_noisy"), ("sisdr_best_mean", "sisdr_best"),
+                           ("sisir_sisdropt_mean", "sisir_sisdropt"),
+                           ("sisar_sisdropt_mean", "sisar_sisdropt"),
+                           ("snr_sisdropt_mean", "snr_sisdropt"))
+
+
 def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
                stoi_best=None, stoi_params=None, snr_stoiopt=None, **quality):
     """One all_results.json row (run_algorithm_on_pair :314-338).  STOI
@@ -77,14 +92,15 @@ def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
     (all or none: segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best, fwsegsnr_params,
     snr_fwsegopt) add the QUALITY_KEYS of a quality=True sweep, the distortion
     keywords (all or none: DISTORTION_ARGS) the DISTORTION_KEYS of a
-    distortion=True one."""
+    distortion=True one, the separation keywords (all or none: SEPARATION_ARGS)
+    the SEPARATION_KEYS of a separation=True one."""
     row = {k: None for k in ROW_KEYS}
     row.update(alg=alg, stem=stem, sr=int(sr), snr_noisy=snr_noisy,
                best_params_stoi=dict(stoi_params or {}), best_params_pesq={},
                best_params_balanced={}, snr_snropt=best_snr,
                best_params_snr=dict(best_params or {}),
                stoi_noisy=stoi_noisy, stoi_stoiopt=stoi_best, snr_stoiopt=snr_stoiopt)
-    unknown = set(quality) - set(QUALITY_ARGS) - set(DISTORTION_ARGS)
+    unknown = set(quality) - set(QUALITY_ARGS) - set(DISTORTION_ARGS) - set(SEPARATION_ARGS)
     if unknown:
         raise TypeError(f"result_row: unexpected keywords {sorted(unknown)}")
     if set(quality) & set(QUALITY_ARGS):
@@ -98,6 +114,12 @@ def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
                    llr_best=quality.get("llr_best"),
                    best_params_llr=dict(quality.get("llr_params") or {}),
                    snr_llropt=quality.get("snr_llropt"))
+    if set(quality) & set(SEPARATION_ARGS):
+        row.update(sisdr_noisy=quality.get("sisdr_noisy"), sisdr_best=quality.get("sisdr_best"),
+                   sisir_sisdropt=quality.get("sisir_sisdropt"),
+                   sisar_sisdropt=quality.get("sisar_sisdropt"),
+                   best_params_sisdr=dict(quality.get("sisdr_params") or {}),
+                   snr_sisdropt=quality.get("snr_sisdropt"))
     return row
 
 
@@ -122,6 +144,9 @@ def summary_means(all_results, algorithms):
                 entry[key] = safe_mean([r.get(field) for r in rows])
         if any("llr_best" in r for r in rows):  # a distortion=True sweep
             for key, field in DISTORTION_SUMMARY_KEYS:
+                entry[key] = safe_mean([r.get(field) for r in rows])
+        if any("sisdr_best" in r for r in rows):  # a separation=True sweep
+            for key, field in SEPARATION_SUMMARY_KEYS:
                 entry[key] = safe_mean([r.get(field) for r in rows])
         out[alg] = entry
     return out

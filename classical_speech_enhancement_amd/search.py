@@ -52,6 +52,14 @@ of include/cse_lpc.h, the log-likelihood ratio and the cepstrum distance
 columns 8 and 9 (DISTORTION_COLUMNS) of a table that then always has NCOL + 4
 columns: columns 6 and 7 are the quality columns, NaN unless quality=True is
 given too.  "llr" and "cep" are objectives that are minimised.
+
+separation=True (the same four functions) adds the scale-invariant SDR of
+include/cse_sisdr.h and its two parts, SI-SIR (what is left of the noise) and
+SI-SAR (what the algorithm added), from cse_sisdr_cells with the pair's own
+noisy - clean as the interference: columns 10 to 12 (SEPARATION_COLUMNS) of a
+table that then always has NCOL + 7 columns, the quality and distortion columns
+NaN unless asked for too.  "sisdr", "sisir" and "sisar" are maximised; a value
+that is not finite (NaN, +inf, -inf) is skipped.
 """
 
 import math
@@ -68,7 +76,9 @@ ALGO_WEIGHT = {"spectralSubtractor": 1.0, "wiener": 1.1, "mmse": 2.0, "omlsa": 3
 # segsnr / fwsegsnr (dB): the reference's step for PESQ, the quality objective they stand in for
 # llr / cep: that PESQ step of 1e-3 on a 5-wide scale carried to a 2-wide and a 10-wide one
 TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5,
-             "segsnr": 1e-3, "fwsegsnr": 1e-3, "llr": 1e-4, "cep": 1e-3}
+             "segsnr": 1e-3, "fwsegsnr": 1e-3, "llr": 1e-4, "cep": 1e-3,
+             # sisdr / sisir / sisar (dB): the step of the other dB objectives
+             "sisdr": 1e-3, "sisir": 1e-3, "sisar": 1e-3}
 
 # one float64 row per cell.  lag: finalize_enhanced's alignment lag (0 when
 # not aligned); xstatus: cse_xcorr_lag's status (engine: XCORR_OK, XCORR_FLAT =
@@ -81,16 +91,22 @@ NCOL = len(RECORD_FIELDS) - 1
 QUALITY_COLUMNS = {"segsnr": 6, "fwsegsnr": 7}
 # where select_best's scan starts: the reference's -1 (speech_enhancement_comparison.py:126-141)
 # unless the objective's values go below it (dB scores clamped to [-10, 35])
-SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf, "llr": -math.inf, "cep": -math.inf}
+SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf, "llr": -math.inf, "cep": -math.inf,
+              "sisdr": -math.inf, "sisir": -math.inf, "sisar": -math.inf}
 # distortion=True tables have NCOL + 4 columns: the two quality columns (NaN
 # without quality=True), then these.  Lower is better: select_best scans the
 # negated column
 DISTORTION_COLUMNS = {"llr": 8, "cep": 9}
+# separation=True tables have NCOL + 7 columns: the quality and distortion
+# columns (NaN unless asked for too), then these.  Unbounded dB values that may
+# be +-inf or NaN (include/cse_sisdr.h): select_best skips what is not finite
+SEPARATION_COLUMNS = {"sisdr": NCOL + 4, "sisir": NCOL + 5, "sisar": NCOL + 6}
 
 
-def table_width(quality=False, distortion=False):
-    """Columns of a table: NCOL, + 2 with quality, + 4 with distortion (either way)."""
-    return NCOL + (4 if distortion else 2 if quality else 0)
+def table_width(quality=False, distortion=False, separation=False):
+    """Columns of a table: NCOL, + 2 with quality, + 4 with distortion (with or
+    without quality), + 7 with separation (whatever else is asked for)."""
+    return NCOL + (7 if separation else 4 if distortion else 2 if quality else 0)
 # bound on the cell waveforms held at once for STOI scoring (f32 bytes): 48 GiB
 # of the 288 GB HBM, i.e. 10 full 10-s pairs (7,308 computed cells x 640 KB each)
 # per batch, two batches in flight.  100-pair sweep (late r04, call_r04s.sh in profiles/r04_commands.md):
@@ -304,7 +320,7 @@ def _unique_inverse(x):
 
 
 def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True, quality=False,
-                   distortion=False):
+                   distortion=False, separation=False):
     """Device compute of the cells ``ids``: per-cell (sse, snr, finite, stoi,
     lag, xstatus), scored after finalize_enhanced's alignment (align=False: at
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
@@ -313,7 +329,10 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     cell is not finite), scored on the side stream from the same waveforms,
     with or without STOI.  distortion=True makes the rows NCOL + 4 wide and
     fills llr and cep (DISTORTION_COLUMNS) the same way; the quality columns
-    are then there too, NaN unless quality=True.
+    are then there too, NaN unless quality=True.  separation=True makes the rows
+    NCOL + 7 wide and fills sisdr, sisir and sisar (SEPARATION_COLUMNS), the
+    interference being the pair's noisy - clean; the quality and distortion
+    columns are NaN unless asked for.
 
     clean/noisy: lists of 1-D float arrays (host) indexed by pair.  Pairs are
     batched by length (the engine's signal batches are rectangular), and, when
@@ -337,7 +356,7 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     size0 = eng.plan_cache_size
     try:
         return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, bool(quality),
-                               bool(distortion))
+                               bool(distortion), bool(separation))
     finally:
         if own:
             eng._plan_cache.clear()
@@ -347,11 +366,13 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
                 eng._plan_cache.popitem(last=False)
 
 
-def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, distortion=False):
+def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, distortion=False,
+                    separation=False):
     import torch
     from .engine import snr_db, spec_fingerprint, structure_digest
-    from .metrics import LpcPlan, SegSnrPlan, StoiPlan
-    keep = bool(stoi) or quality or distortion  # the cell waveforms are scored on the side stream
+    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan
+    # the cell waveforms are scored on the side stream
+    keep = bool(stoi) or quality or distortion or separation
     ids = np.asarray(ids, dtype=np.int64)
     lengths = [len(x) for x in noisy]
     js_specs = isinstance(specs, JobSpecs)
@@ -361,7 +382,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
     else:
         comp, back = ids, np.arange(len(ids))
         pair_of = np.fromiter((specs[c][0] for c in comp), dtype=np.int64, count=len(comp))
-    vals = np.full((len(comp), table_width(quality, distortion)), np.nan)
+    vals = np.full((len(comp), table_width(quality, distortion, separation)), np.nan)
     by_len = OrderedDict()
     upairs, first = np.unique(pair_of, return_index=True)
     for pair in upairs[np.argsort(first, kind="stable")].tolist():  # first-appearance order
@@ -379,14 +400,14 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
     nbatch = 0
 
     def collect(item):
-        rows_, fin_, out_, qout_, dout_, ev_, _refs = item
+        rows_, fin_, out_, qout_, dout_, sout_, ev_, _refs = item
         ev_.synchronize()
         if out_ is not None:
             vals[rows_, 3] = np.where(fin_, out_.cpu().numpy(), np.nan)
-        for first, pair_ in ((NCOL, qout_), (NCOL + 2, dout_)):
+        for first, pair_ in ((NCOL, qout_), (NCOL + 2, dout_), (NCOL + 4, sout_)):
             if pair_ is not None:
-                vals[rows_, first:first + 2] = np.where(np.asarray(fin_, dtype=bool)[:, None],
-                                                        pair_.cpu().numpy(), np.nan)
+                vals[rows_, first:first + pair_.shape[1]] = np.where(
+                    np.asarray(fin_, dtype=bool)[:, None], pair_.cpu().numpy(), np.nan)
 
     sorted_pairs = len(pair_of) < 2 or bool((pair_of[1:] >= pair_of[:-1]).all())
     for L, pairs_l in by_len.items():
@@ -418,10 +439,11 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
             splan = StoiPlan(cl, extended=(stoi == "extended")) if stoi else None
             qplan = SegSnrPlan(cl) if quality else None
             dplan = LpcPlan(cl) if distortion else None
+            pplan = SiSdrPlan(cl, nz) if separation else None
             state = {}
 
             def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, qplan=qplan,
-                        dplan=dplan, state=state):
+                        dplan=dplan, pplan=pplan, state=state):
                 """one n_fft's cells are final: queue their scores on the side stream"""
                 idx = np.asarray(p.idx, dtype=np.int64)
                 lg = lag if lag is not None else np.zeros(len(idx), dtype=np.int64)
@@ -432,7 +454,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
                 lag_d = torch.as_tensor(np.asarray(lg, dtype=np.int32)).cuda()
                 y = p.y_all.view(-1)  # the run's waveform buffer (every n_fft's rows)
                 side.wait_stream(main)
-                out = qout = dout = None
+                out = qout = dout = sout = None
                 with torch.cuda.stream(side):
                     if splan is not None:
                         out = splan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
@@ -440,11 +462,13 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
                         qout = qplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     if dplan is not None:
                         dout = dplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
+                    if pplan is not None:
+                        sout = pplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 state["ev"] = ev
-                inflight.append((js[idx], fin, out, qout, dout, ev,
-                                 (y, off_d, sig_d, lag_d, splan, qplan, dplan)))
+                inflight.append((js[idx], fin, out, qout, dout, sout, ev,
+                                 (y, off_d, sig_d, lag_d, splan, qplan, dplan, pplan)))
                 while len(inflight) > 2:  # bound the STOI scratch held in flight
                     collect(inflight.pop(0))
 
@@ -490,7 +514,8 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
 
 def gather_records(local, n_total, group=None, device=None):
     """All-gather per-cell records [n_local, 1 + NCOL] (RECORD_FIELDS; 1 + NCOL + 2
-    with the quality columns) from every rank into one [n_total, width - 1]
+    with the quality columns, + 4 with the distortion columns, + 7 with the
+    separation columns) from every rank into one [n_total, width - 1]
     table indexed by cell_id.  The width is the records' own (every rank's
     alike).  Fixed-size rows padded to the largest shard so one
     all_gather_into_tensor moves them."""
@@ -545,7 +570,7 @@ def _scan_records(sc, rec, ids, tol, start=-1.0):
     return win, (incumbent if win >= 0 else None)
 
 
-def _select_best_blocks(specs, table, col, tol, start=-1.0, sign=1.0):
+def _select_best_blocks(specs, table, col, tol, start=-1.0, sign=1.0, finite_only=False):
     """select_best over a JobSpecs table: each algorithm's cells of all pairs
     as one [pairs, grid] block (the columns of a (pair, algorithm) run are
     contiguous), running maxima along the grid axis in one call.  sign = -1:
@@ -555,6 +580,8 @@ def _select_best_blocks(specs, table, col, tol, start=-1.0, sign=1.0):
     # is not NaN), as [pairs, cells of one pair]
     sc_all = sign * np.asarray(table[:n_pairs * specs.per_pair, col], dtype=np.float64)
     ok = (table[:n_pairs * specs.per_pair, 2] != 0) & (sc_all == sc_all)
+    if finite_only:
+        ok &= np.isfinite(sc_all)
     sc_all = np.where(ok, sc_all, -np.inf).reshape(n_pairs, specs.per_pair)
     found = {}
     off = 0
@@ -593,7 +620,12 @@ def select_best(specs, table, objective="snr", tol=None):
 
     "llr" / "cep" (a distortion=True table) are minimised: the same scan runs
     on the negated column, started at -inf, so a cell replaces the incumbent
-    when its value < incumbent - tol; the score returned is the value itself."""
+    when its value < incumbent - tol; the score returned is the value itself.
+
+    "sisdr" / "sisir" / "sisar" (a separation=True table) are maximised from
+    -inf like the dB objectives above; a value that is not finite is skipped the
+    way a NaN is (+inf: a test signal that is the clean one scaled, or no
+    interference left, which the tolerance scan could not rank)."""
     best = _select_best(specs, table, objective, tol)
     if objective in DISTORTION_COLUMNS:  # -(-v) is v, bit for bit
         best = OrderedDict((k, (win, None if sc is None else -sc)) for k, (win, sc) in best.items())
@@ -602,7 +634,7 @@ def select_best(specs, table, objective="snr", tol=None):
 
 def _select_best(specs, table, objective, tol):
     tol = TOLERANCE[objective] if tol is None else tol
-    sign = 1.0
+    sign, finite_only = 1.0, False
     if objective in QUALITY_COLUMNS:
         col = QUALITY_COLUMNS[objective]
         if np.ndim(table) != 2 or np.shape(table)[1] <= col:
@@ -613,13 +645,18 @@ def _select_best(specs, table, objective, tol):
         if np.ndim(table) != 2 or np.shape(table)[1] <= col:
             raise ValueError(f"objective {objective!r} needs a distortion=True table of "
                              f"{NCOL + 4} columns, this one has {np.shape(table)[-1]}")
+    elif objective in SEPARATION_COLUMNS:
+        col, finite_only = SEPARATION_COLUMNS[objective], True
+        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
+            raise ValueError(f"objective {objective!r} needs a separation=True table of "
+                             f"{NCOL + 7} columns, this one has {np.shape(table)[-1]}")
     elif objective in ("snr", "stoi"):
         col = TABLE_COLUMN[objective]
     else:
         raise ValueError(f"objective {objective!r} is not scored on the device (pesq is absent)")
     scan_start = SCAN_START.get(objective, -1.0)
     if isinstance(specs, JobSpecs) and tol >= 0.0:
-        return _select_best_blocks(specs, table, col, tol, scan_start, sign)
+        return _select_best_blocks(specs, table, col, tol, scan_start, sign, finite_only)
     groups = OrderedDict()
     if isinstance(specs, JobSpecs):  # (pair, algorithm) runs are contiguous
         per = [len(specs.cells[a]) for a in specs.algorithms]
@@ -636,6 +673,8 @@ def _select_best(specs, table, objective, tol):
         ids = np.asarray(ids, dtype=np.int64)
         sc = sign * table[ids, col]
         ok = (table[ids, 2] != 0) & (sc == sc)  # finite cell, score not NaN
+        if finite_only:
+            ok &= np.isfinite(sc)
         sc = np.where(ok, sc, -np.inf)
         incumbent, win = scan_start, -1
         if tol >= 0.0 and len(sc):
@@ -660,7 +699,7 @@ def _select_best(specs, table, objective, tol):
 
 
 def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
-             extended=False, quality=False, distortion=False):
+             extended=False, quality=False, distortion=False, separation=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
@@ -671,7 +710,9 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     the table has NCOL + 2 columns (QUALITY_COLUMNS: segsnr, fwsegsnr), filled
     by the default compute; a caller's compute function returns them itself.
     distortion=True: NCOL + 4 columns (the quality columns, NaN without
-    quality=True, then DISTORTION_COLUMNS: llr, cep), likewise."""
+    quality=True, then DISTORTION_COLUMNS: llr, cep), likewise.
+    separation=True: NCOL + 7 columns (the quality and distortion columns, NaN
+    unless asked for, then SEPARATION_COLUMNS: sisdr, sisir, sisar), likewise."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
@@ -679,18 +720,19 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     lengths = [len(x) for x in noisy]
     rank_of, _ = assign_shards(specs, lengths, world)
     ids = np.nonzero(rank_of == rank)[0]
-    ncol = table_width(quality, distortion)
-    if compute is None and (extended or quality or distortion):
+    ncol = table_width(quality, distortion, separation)
+    if compute is None and (extended or quality or distortion or separation):
         def compute(clean, noisy, specs, ids):
             return engine_compute(clean, noisy, specs, ids,
                                   stoi="extended" if extended else True, quality=quality,
-                                  distortion=distortion)
+                                  distortion=distortion, separation=separation)
     compute = compute or engine_compute
     vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, ncol))
     if np.ndim(vals) != 2 or np.shape(vals)[1] != ncol:
         raise ValueError(f"compute returned rows of shape {np.shape(vals)}, expected "
                          f"{ncol} columns (quality={bool(quality)}"
-                         + (", distortion=True)" if distortion else ")"))
+                         + (", distortion=True" if distortion else "")
+                         + (", separation=True)" if separation else ")"))
     if not dist_on and len(ids) == len(specs):  # one process, every cell in order: no gather
         table = np.asarray(vals, dtype=np.float64)
     else:
@@ -722,13 +764,25 @@ def _device_distortion(clean, test, sr):
     return calculate_llr(clean, test, sr), calculate_cep(clean, test, sr)
 
 
+def _device_separation(clean, noisy, sr):
+    """SI-SDR of the noisy input against clean on the device, None for a failure."""
+    from .metrics import calculate_sisdr
+    return calculate_sisdr(clean, noisy, sr)
+
+
 def _opt(v):
     return None if v != v else float(v)
 
 
+def _finite(v):
+    """A separation score for a result row: None unless finite (JSON has no inf)."""
+    return float(v) if math.isfinite(v) else None
+
+
 def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_ranges=None,
                         compute=None, stoi_fn=None, extended=False, quality=False,
-                        quality_fn=None, distortion=False, distortion_fn=None):
+                        quality_fn=None, distortion=False, distortion_fn=None, separation=False,
+                        separation_fn=None):
     """Single-pair, single-algorithm mirror of the reference's
     optimize_parameters (speech_enhancement_comparison.py:109-252), scored by
     STOI and SNR: returns {'stoi': {'score', 'params', 'cell', 'snr'},
@@ -746,7 +800,12 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     and improvements.
     distortion=True: likewise 'llr' and 'cep' entries from the two distortion
     columns (distortion_fn(clean, noisy, sr) -> (llr, cep) for the baselines);
-    both are minimised, so their improvement is baseline - score."""
+    both are minimised, so their improvement is baseline - score.
+    separation=True: likewise 'sisdr', 'sisir' and 'sisar' entries from the
+    three separation columns, each carrying the other two scores of its cell.
+    Only 'sisdr' has a baseline and an improvement (separation_fn(clean, noisy,
+    sr) -> the noisy input's SI-SDR; default: the device): the noisy input has
+    no artifacts to compare with."""
     from .engine import canonical_algo
     if sr != 16000:
         raise ValueError("the device path runs at 16 kHz (prepare_pair resamples to 16 kHz)")
@@ -756,7 +815,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     clean = [np.asarray(clean_reference, np.float64)]
     noisy = [np.asarray(noisy_audio, np.float64)]
     table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended,
-                           quality=quality, distortion=distortion)
+                           quality=quality, distortion=distortion, separation=separation)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -803,11 +862,26 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
                          "snr": float(table[did, 1])}
             out["baseline"][name] = base_d[k] or 0
             out["improvements"][name] = out["baseline"][name] - dscore
+    if separation:
+        for name in SEPARATION_COLUMNS:
+            out[name] = None
+            pid, pscore = select_best(specs, table, name)[(0, alg)]
+            if pid < 0:
+                continue
+            out[name] = {"score": pscore, "params": dict(specs[pid][2]), "cell": int(pid),
+                         "snr": float(table[pid, 1])}
+            out[name].update({k: _finite(table[pid, c]) for k, c in SEPARATION_COLUMNS.items()
+                              if k != name})
+            if name == "sisdr":
+                base_p = (separation_fn or _device_separation)(clean[0], noisy[0], sr)
+                out["baseline"][name] = base_p or 0
+                out["improvements"][name] = pscore - out["baseline"][name]
     return out
 
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
-              group=None, device=None, extended=False, quality=False, distortion=False):
+              group=None, device=None, extended=False, quality=False, distortion=False,
+              separation=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
@@ -827,23 +901,30 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     distance; the LLR-best (lowest) cell's waveform is written as
     ..._optimized_llr.wav and each row gains llr_noisy, cep_noisy, llr_best,
     best_params_llr and snr_llropt (means in summary_means.json).  The CEP
-    winner is select_best(specs, table, "cep")'s."""
+    winner is select_best(specs, table, "cep")'s.
+    separation=True: the cells are also scored by SI-SDR, SI-SIR and SI-SAR
+    against the pair's own noisy - clean; the SI-SDR-best cell's waveform is
+    written as ..._optimized_sisdr.wav and each row gains sisdr_noisy,
+    sisdr_best, that cell's sisir_sisdropt and sisar_sisdropt (how its error
+    splits), best_params_sisdr and snr_sisdropt (means in summary_means.json).
+    The SI-SIR and SI-SAR winners are select_best's."""
     import torch
     import torch.distributed as dist
     from . import results
     from .engine import Engine
-    from .metrics import LpcPlan, SegSnrPlan, StoiPlan
+    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan
     grids = grids or ALGORITHM_GRIDS
     algorithms = list(algorithms or grids)
     specs = job_specs(len(noisy), algorithms, grids)
     table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
-                           quality=quality, distortion=distortion)
+                           quality=quality, distortion=distortion, separation=separation)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
     best_stoi = select_best(specs, table, "stoi")
     best_fw = select_best(specs, table, "fwsegsnr") if quality else None
     best_llr = select_best(specs, table, "llr") if distortion else None
+    best_sdr = select_best(specs, table, "sisdr") if separation else None
     eng = Engine()
     rows = []
     for pair, stem in enumerate(stems):
@@ -862,6 +943,10 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         if distortion:
             dplan = LpcPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
             d_noisy = [_opt(v) for v in dplan.score(nf, [0], [0], clip=False)[0]]
+        p_noisy = None
+        if separation:
+            pplan = SiSdrPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
+            p_noisy = _finite(pplan.score(nf, [0], [0], clip=False)[0, 0])
         x = torch.as_tensor(n).cuda().view(1, -1)
         cl = torch.as_tensor(c).cuda().view(1, -1)
         for alg in algorithms:
@@ -873,7 +958,9 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
             os.makedirs(out_dir, exist_ok=True)
             fid, fscore = best_fw[(pair, alg)] if quality else (-1, None)
             lid, lscore = best_llr[(pair, alg)] if distortion else (-1, None)
-            for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid), ("llr", lid)):
+            pid, pscore = best_sdr[(pair, alg)] if separation else (-1, None)
+            for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid), ("llr", lid),
+                           ("sisdr", pid)):
                 if k < 0:
                     continue
                 res = eng.run(x, [(0, alg, specs[k][2])], clean=cl, want_waveforms=True, align=True)
@@ -895,7 +982,14 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                     llr_noisy=d_noisy[0], cep_noisy=d_noisy[1],
                     llr_best=None if lid < 0 else float(lscore),
                     llr_params=None if lid < 0 else specs[lid][2],
-                    snr_llropt=None if lid < 0 else float(table[lid, 1])))))
+                    snr_llropt=None if lid < 0 else float(table[lid, 1]))),
+                **({} if not separation else dict(
+                    sisdr_noisy=p_noisy,
+                    sisdr_best=None if pid < 0 else float(pscore),
+                    sisir_sisdropt=None if pid < 0 else _finite(table[pid, NCOL + 5]),
+                    sisar_sisdropt=None if pid < 0 else _finite(table[pid, NCOL + 6]),
+                    sisdr_params=None if pid < 0 else specs[pid][2],
+                    snr_sisdropt=None if pid < 0 else float(table[pid, 1])))))
             if extended:
                 rows[-1]["stoi_extended"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
