@@ -1,7 +1,7 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
-include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h
-and include/cse_sisdr.h).
+include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
+include/cse_sisdr.h and include/cse_logerr.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -99,6 +99,15 @@ class ImcraParams(ctypes.Structure):
 
 assert ctypes.sizeof(ImcraParams) == 80
 
+
+class LogErrParams(ctypes.Structure):
+    """cse_logerr_params_t (include/cse_logerr.h): what the noise-PSD score reads."""
+    _fields_ = [("floor", ctypes.c_double), ("t0", ctypes.c_int32), ("bin_lo", ctypes.c_int32),
+                ("bin_hi", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(LogErrParams) == 24
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -128,6 +137,9 @@ EXPORTS_LPC = ("cse_lpc_workspace_bytes", "cse_lpc_prepare", "cse_lpc_scratch_by
 # include/cse_sisdr.h (SI-SDR, SI-SIR and SI-SAR), likewise
 EXPORTS_SISDR = ("cse_sisdr_workspace_bytes", "cse_sisdr_prepare", "cse_sisdr_scratch_bytes",
                  "cse_sisdr_cells")
+# include/cse_logerr.h (noise-PSD logarithmic estimation error), likewise
+EXPORTS_LOGERR = ("cse_logerr_default_params", "cse_logerr_reference", "cse_logerr_scratch_bytes",
+                  "cse_logerr_rows")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -257,6 +269,14 @@ def load(path=LIB_PATH):
     lib.cse_sisdr_scratch_bytes.argtypes = [i64, i64]
     lib.cse_sisdr_cells.restype = i32
     lib.cse_sisdr_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, P, P, P, P, P, P, P]
+    lib.cse_logerr_default_params.restype = None
+    lib.cse_logerr_default_params.argtypes = [P, i32]
+    lib.cse_logerr_reference.restype = i32
+    lib.cse_logerr_reference.argtypes = [P, i64, i32, i32, f64, P, P]
+    lib.cse_logerr_scratch_bytes.restype = i64
+    lib.cse_logerr_scratch_bytes.argtypes = [i64, i32]
+    lib.cse_logerr_rows.restype = i32
+    lib.cse_logerr_rows.argtypes = [P, i64, i32, i32, P, P, P, P, i64, P, P, P, P, P, P, P]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

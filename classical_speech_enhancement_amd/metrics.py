@@ -41,8 +41,14 @@ SiSdrPlan scores the scale-invariant SDR of include/cse_sisdr.h (Le Roux et al.
 2019) and, when the batch's noisy signals are given, its split into SI-SIR
 (residual interference) and SI-SAR (artifacts) through cse_sisdr_prepare /
 cse_sisdr_cells, with the same lag / clip test-signal definition, at any rate.
+
+NoiseErrPlan scores noise-PSD estimates, not waveforms: the logarithmic
+estimation error of include/cse_logerr.h against the smoothed power of
+noisy - clean (cse_logerr_reference / cse_logerr_rows), split into over- and
+under-estimation, per row and on request per frame.
 """
 
+import ctypes
 import math
 
 import numpy as np
@@ -452,6 +458,131 @@ def calculate_sisdr(clean_reference, test_audio, sr):
             raise ValueError("SI-SDR is undefined (an all-zero signal)")
         return v
     return _calculate_quality(fn, "SI-SDR", clean_reference, test_audio, sr)
+
+
+class NoiseErrPlan:
+    """Reference side of the noise-PSD logarithmic estimation error
+    (include/cse_logerr.h) for S equal-length pairs (clean, noisy: [S, L] f64
+    cuda): the power of STFT(noisy - clean) at (n_fft, hop_length), smoothed
+    over frames with ``beta`` (cse_logerr_reference).  ``R`` ([S, T, B] f64
+    cuda) is that reference PSD, ``T`` and ``B`` its frames and bins.  floor,
+    skip_frames (the first scored frame) and bins ((lo, hi), default every bin)
+    are what every score() of the plan uses.  beta = 0.9 is this project's
+    default, a time constant of about 80 ms at the grid's 8-ms hop."""
+
+    def __init__(self, clean, noisy, n_fft, hop_length, beta=0.9, floor=1e-12, skip_frames=0,
+                 bins=None):
+        if not _gpu_visible():
+            raise _lib.CseError("no GPU visible: the HIP engine has no CPU fallback")
+        from .engine import Engine
+        for name, x in (("clean", clean), ("noisy", noisy)):
+            if not torch.is_tensor(x) or x.dtype != torch.float64 or x.dim() != 2 or \
+                    not x.is_cuda:
+                raise ValueError(f"{name} must be a [S, L] float64 cuda tensor")
+        if noisy.shape != clean.shape or noisy.device != clean.device:
+            raise ValueError("noisy must have clean's shape and device")
+        eng = Engine(clean.device)
+        self.lib = eng.lib
+        self.S = int(clean.shape[0])
+        _, Pv = eng.stft(noisy.contiguous(), int(n_fft), int(hop_length), x_sub=clean.contiguous(),
+                         want_y=False)
+        self.T, self.B = int(Pv.shape[1]), int(Pv.shape[2])
+        self.prm = _lib.LogErrParams()
+        self.lib.cse_logerr_default_params(ctypes.byref(self.prm), self.B)
+        self.prm.floor = float(floor)
+        self.prm.t0 = int(skip_frames)
+        if bins is not None:
+            self.prm.bin_lo, self.prm.bin_hi = int(bins[0]), int(bins[1])
+        self.beta = float(beta)
+        self.R = torch.empty_like(Pv)
+        _lib.check(self.lib.cse_logerr_reference(_ptr(Pv), self.S, self.T, self.B, self.beta,
+                                                 _ptr(self.R), _stream()), "cse_logerr_reference")
+
+    def _rows(self, N):
+        if not torch.is_tensor(N) or N.dtype != torch.float32 or not N.is_cuda or \
+                N.device != self.R.device:
+            raise ValueError("an estimate must be a float32 cuda tensor on the plan's device")
+        if N.dim() == 3 and tuple(N.shape[1:]) == (self.T, self.B):
+            return N.contiguous(), self.T * self.B, self.B
+        if N.dim() == 2 and int(N.shape[1]) == self.B:
+            return N.contiguous(), self.B, 0
+        raise ValueError(f"an estimate must be [n, {self.T}, {self.B}] or [n, {self.B}], "
+                         f"found {tuple(N.shape)}")
+
+    def score(self, N, sig_of=None, per_frame=False):
+        """N: f32 cuda [n, T, B] (time-varying estimates) or [n, B] (static
+        ones), or a list mixing both, the rows counted through the list.
+        sig_of: the signal of every row (default 0..S-1 when n == S).  Returns
+        float64 numpy [n, 3] of (logerr, over, under) in dB, logerr = over +
+        under; per_frame=True also returns [n, 2, T] (frame_over, frame_under;
+        NaN before skip_frames).  Values follow include/cse_logerr.h's IEEE
+        rules; a wrong shape raises ValueError."""
+        parts = [self._rows(x) for x in (N if isinstance(N, (list, tuple)) else [N])]
+        n = sum(int(p[0].shape[0]) for p in parts)
+        if sig_of is None:
+            if n != self.S:
+                raise ValueError(f"sig_of is needed: {n} rows for {self.S} signals")
+            sig_of = np.arange(self.S)
+        sig_h = np.asarray(sig_of, dtype=np.int32).reshape(-1)
+        if len(sig_h) != n:
+            raise ValueError(f"sig_of has {len(sig_h)} entries for {n} rows")
+        if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= self.S):
+            raise ValueError("sig_of out of range")
+        dev = self.R.device
+        cols = torch.empty((2, n), dtype=torch.float64, device=dev)
+        fr = torch.empty((2, n, self.T), dtype=torch.float64, device=dev) if per_frame else None
+        done = 0
+        for x, row_stride, t_stride in parts:
+            m = int(x.shape[0])
+            if m == 0:
+                continue
+            off = torch.arange(m, dtype=torch.int64, device=dev) * row_stride
+            st = torch.full((m,), t_stride, dtype=torch.int64, device=dev)
+            sig = torch.as_tensor(sig_h[done:done + m], device=dev)
+            nbytes = int(self.lib.cse_logerr_scratch_bytes(m, self.T))
+            scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            _lib.check(self.lib.cse_logerr_rows(
+                _ptr(self.R), self.S, self.T, self.B, _ptr(x), _ptr(off), _ptr(st), _ptr(sig), m,
+                ctypes.byref(self.prm), _ptr(scratch), _ptr(cols[0, done:]), _ptr(cols[1, done:]),
+                None if fr is None else _ptr(fr[0, done:]),
+                None if fr is None else _ptr(fr[1, done:]), _stream()), "cse_logerr_rows")
+            done += m
+        c = cols.cpu().numpy()
+        table = np.empty((n, 3), dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            table[:, 0] = c[0] + c[1]
+        table[:, 1], table[:, 2] = c[0], c[1]
+        if not per_frame:
+            return table
+        return table, np.ascontiguousarray(fr.cpu().numpy().transpose(1, 0, 2))
+
+
+def noise_logerr(clean, noisy, N, n_fft, hop_length, per_frame=False, **kw):
+    """LogErr in dB (include/cse_logerr.h) of one noise-PSD estimate N of the
+    pair (clean, noisy), numpy in and out.  N is shaped as
+    plugins.noise_estimation returns it: (B, T), (B, 1) or (B,).  kw: beta,
+    floor, skip_frames, bins of NoiseErrPlan.  Returns {logerr, over, under},
+    with per_frame=True also frame_over and frame_under ([T])."""
+    c = np.asarray(clean, dtype=np.float64)
+    z = np.asarray(noisy, dtype=np.float64)
+    if c.ndim != 1 or c.shape != z.shape or c.size == 0:
+        raise ValueError("clean and noisy must be non-empty 1-D signals of equal length")
+    plan = NoiseErrPlan(torch.as_tensor(c).cuda().view(1, -1), torch.as_tensor(z).cuda().view(1, -1),
+                        n_fft, hop_length, **kw)
+    N = np.asarray(N, dtype=np.float32)
+    if N.ndim == 1:
+        N = N[:, None]
+    if N.ndim != 2 or N.shape[0] != plan.B or N.shape[1] not in (1, plan.T):
+        raise ValueError(f"N must be ({plan.B}, {plan.T}), ({plan.B}, 1) or ({plan.B},), "
+                         f"found {N.shape}")
+    Nd = torch.as_tensor(np.ascontiguousarray(N.T)).cuda()
+    Nd = Nd.view(1, plan.B) if N.shape[1] == 1 and plan.T != 1 else Nd.view(1, plan.T, plan.B)
+    res = plan.score(Nd, [0], per_frame=per_frame)
+    t = res[0] if per_frame else res
+    out = {"logerr": float(t[0, 0]), "over": float(t[0, 1]), "under": float(t[0, 2])}
+    if per_frame:
+        out["frame_over"], out["frame_under"] = res[1][0, 0], res[1][0, 1]
+    return out
 
 
 def _plan_pair(cls, x, y, fs, which):

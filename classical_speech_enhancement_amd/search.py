@@ -60,6 +60,13 @@ noisy - clean as the interference: columns 10 to 12 (SEPARATION_COLUMNS) of a
 table that then always has NCOL + 7 columns, the quality and distortion columns
 NaN unless asked for too.  "sisdr", "sisir" and "sisar" are maximised; a value
 that is not finite (NaN, +inf, -inf) is skipped.
+
+score_noise_estimators and sweep_tracker judge noise-PSD estimates themselves,
+with no enhancement algorithm on top: the logarithmic estimation error of
+include/cse_logerr.h (cse_logerr_rows) against the smoothed power of the pair's
+own noisy - clean, split into over- and under-estimation.  sweep_tracker
+enumerates one tracker's parameter sets in grid_cells' order and applies the
+sequential best-so-far rule to the mean over pairs, minimised.
 """
 
 import math
@@ -78,7 +85,9 @@ ALGO_WEIGHT = {"spectralSubtractor": 1.0, "wiener": 1.1, "mmse": 2.0, "omlsa": 3
 TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5,
              "segsnr": 1e-3, "fwsegsnr": 1e-3, "llr": 1e-4, "cep": 1e-3,
              # sisdr / sisir / sisar (dB): the step of the other dB objectives
-             "sisdr": 1e-3, "sisir": 1e-3, "sisar": 1e-3}
+             "sisdr": 1e-3, "sisir": 1e-3, "sisar": 1e-3,
+             # logerr (dB, sweep_tracker's objectives): the step of the other dB objectives
+             "logerr": 1e-3}
 
 # one float64 row per cell.  lag: finalize_enhanced's alignment lag (0 when
 # not aligned); xstatus: cse_xcorr_lag's status (engine: XCORR_OK, XCORR_FLAT =
@@ -739,6 +748,116 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
         local = np.concatenate([ids[:, None].astype(np.float64), vals], axis=1)
         table = gather_records(local, len(specs), group=group, device=device)
     return table, select_best(specs, table, objective)
+
+
+NOISE_METHODS = ("percentile", "min_tracking", "true_noise", "mcra", "spp", "minstat", "imcra")
+# bound on the noise-PSD estimates score_noise_estimators holds at once (f32
+# bytes): 4 GiB, 32 estimates of 100 10-s pairs at n_fft 512 / hop 128
+NOISE_EST_BYTES = 4 << 30
+LOGERR_COLUMNS = {"logerr": 0, "over": 1, "under": 2}
+
+
+def score_noise_estimators(clean, noisy, estimators, n_fft=512, hop_length=128, eps=1e-10,
+                           engine=None, **logerr_kw):
+    """LogErr (include/cse_logerr.h) of noise-PSD estimators on pairs.
+
+    clean, noisy: lists of numpy signals as run_grid takes them (a pair is cut
+    to its shorter side); estimators: a list of (method, params), method one of
+    NOISE_METHODS and params what Engine.noise_estimate takes for it.  Pairs
+    are batched by equal length; per batch there is one metrics.NoiseErrPlan
+    (logerr_kw: beta, floor, skip_frames, bins) and every estimate is made once
+    with Engine.noise_estimate (true_noise from the power of noisy - clean),
+    NOISE_EST_BYTES of estimates at a time.  Returns float64
+    [pairs][estimators][3] of (logerr, over, under) in dB."""
+    import torch
+    from .engine import Engine
+    from .metrics import NoiseErrPlan
+    estimators = [(m, dict(p or {})) for m, p in estimators]
+    for m, _ in estimators:
+        if m not in NOISE_METHODS:
+            raise ValueError(f"unknown noise method {m!r}: one of {NOISE_METHODS}")
+    if len(clean) != len(noisy):
+        raise ValueError("clean and noisy differ in number")
+    eng = engine or Engine()
+    out = np.full((len(clean), len(estimators), 3), np.nan)
+    by_len = OrderedDict()
+    for i, (c, z) in enumerate(zip(clean, noisy)):
+        by_len.setdefault(min(len(c), len(z)), []).append(i)
+    for L, idx in by_len.items():
+        cd = torch.as_tensor(np.stack([np.asarray(clean[i], dtype=np.float64)[:L] for i in idx]),
+                             device=eng.device)
+        zd = torch.as_tensor(np.stack([np.asarray(noisy[i], dtype=np.float64)[:L] for i in idx]),
+                             device=eng.device)
+        plan = NoiseErrPlan(cd, zd, n_fft, hop_length, **logerr_kw)
+        S = len(idx)
+        _, P = eng.stft(zd, n_fft, hop_length, want_y=False)
+        Pv = None
+        per = max(1, NOISE_EST_BYTES // (S * plan.T * plan.B * 4))
+        for k0 in range(0, len(estimators), per):
+            chunk = estimators[k0:k0 + per]
+            rows = []
+            for m, prm in chunk:
+                if m == "true_noise":
+                    if Pv is None:
+                        _, Pv = eng.stft(zd, n_fft, hop_length, x_sub=cd, want_y=False)
+                    rows.append(eng.noise_estimate(m, Pv, eps=eps, frames=plan.T, **prm))
+                else:
+                    rows.append(eng.noise_estimate(m, P, eps=eps, **prm))
+            sig = np.tile(np.arange(S), len(chunk))
+            t = plan.score(rows, sig).reshape(len(chunk), S, 3)
+            out[idx, k0:k0 + len(chunk)] = t.transpose(1, 0, 2)
+            del rows
+    return out
+
+
+def select_tracker(means, tol):
+    """The sequential best-so-far rule (select_best's semantics) on per-set
+    means that are minimised: a later set replaces the incumbent only if it is
+    better by more than tol; a mean that is not finite is skipped.  Returns the
+    index of the winner, or -1."""
+    incumbent, win = math.inf, -1
+    for k, v in enumerate(np.asarray(means, dtype=np.float64).tolist()):
+        if math.isfinite(v) and v < incumbent - tol:
+            incumbent, win = v, k
+    return win
+
+
+def sweep_tracker(clean, noisy, method, ranges, objective="logerr", tol=None, n_fft=512,
+                  hop_length=128, eps=1e-10, compute=None, **logerr_kw):
+    """Tune one noise tracker on pairs by the LogErr of its estimate.
+
+    ranges: a dict of lists, enumerated by parameter_ranges.grid_cells in the
+    reference's order; every set is one (method, params) of
+    score_noise_estimators.  objective: "logerr", "over" or "under", the mean
+    over pairs, minimised; the winner is chosen by select_tracker with tol
+    (default TOLERANCE["logerr"]), so ties within tol keep the earlier set and
+    a set whose mean is not finite is skipped.  compute(clean, noisy,
+    estimators) -> [pairs][sets][3] replaces score_noise_estimators (tests).
+    Returns {"table", "means" ([sets] of the objective), "best_index" (-1 when
+    no set has a finite mean), "best_params" (None then), "params" (every set)}.
+    The sweep runs on one device; sharding it over ranks is not built."""
+    if objective not in LOGERR_COLUMNS:
+        raise ValueError(f"objective {objective!r}: one of {tuple(LOGERR_COLUMNS)}")
+    if method not in NOISE_METHODS:
+        raise ValueError(f"unknown noise method {method!r}: one of {NOISE_METHODS}")
+    tol = TOLERANCE["logerr"] if tol is None else tol
+    cells = grid_cells(ranges)
+    ests = [(method, p) for p in cells]
+    if compute is None:
+        table = score_noise_estimators(clean, noisy, ests, n_fft=n_fft, hop_length=hop_length,
+                                       eps=eps, **logerr_kw)
+    else:
+        table = compute(clean, noisy, ests)
+    table = np.asarray(table, dtype=np.float64)
+    if table.shape != (len(clean), len(cells), 3):
+        raise ValueError(f"compute returned shape {table.shape}, expected "
+                         f"{(len(clean), len(cells), 3)}")
+    with np.errstate(invalid="ignore"):
+        means = table[:, :, LOGERR_COLUMNS[objective]].mean(axis=0) if len(clean) else \
+            np.full(len(cells), np.nan)
+    win = select_tracker(means, tol)
+    return {"table": table, "means": means, "best_index": win,
+            "best_params": dict(cells[win]) if win >= 0 else None, "params": cells}
 
 
 def _snr_baseline(c, n):

@@ -7,6 +7,10 @@ so benches and parity tests run on speech-like synthetic clips:
   * noisy: clean + white (even i) or pink (odd i) noise at SNR ~ U[-5, 15] dB,
     clipped to ±1, plus 1e-6 dither so no two frame energies tie.
 Pair i uses ``np.random.default_rng(1000 + i)``.
+
+make_pair_nonstationary keeps that clean signal and adds noise whose level
+steps or ramps (``np.random.default_rng(2000 + i)``): what the noise trackers
+are for, and what the LogErr score of include/cse_logerr.h shows per frame.
 """
 
 import numpy as np
@@ -53,6 +57,31 @@ def make_pair(i, seconds=10.0, sr=16000):
     p_n = np.mean(noise ** 2)
     noise *= np.sqrt(p_s / (p_n * 10 ** (snr_db / 10.0)))
     noisy = np.clip(clean + noise, -1.0, 1.0) + 1e-6 * rng.standard_normal(n)
+    return clean, noisy
+
+
+def make_pair_nonstationary(i, seconds=10.0, sr=16000, kind="step", change_db=15.0, at=0.5):
+    """A pair whose noise level moves, for the noise trackers: make_pair's clean
+    signal and, from ``np.random.default_rng(2000 + i)``, white (even i) or pink
+    (odd i) noise at SNR ~ U[0, 10] dB against the clean power, with a gain in
+    dB on top: kind="step": change_db from sample int(at * n) on;
+    kind="ramp": change_db * k / n at sample k.  Clipped and dithered like
+    make_pair.  Returns (clean, noisy) float64."""
+    if kind not in ("step", "ramp"):
+        raise ValueError(f"kind={kind!r}: 'step' or 'ramp'")
+    clean = make_pair(i, seconds, sr)[0]
+    n = len(clean)
+    rng = np.random.default_rng(2000 + i)
+    noise = rng.standard_normal(n) if i % 2 == 0 else _pink(rng, n)
+    snr_db = rng.uniform(0.0, 10.0)
+    p_s = np.mean(clean ** 2)
+    p_n = np.mean(noise ** 2)
+    noise *= np.sqrt(p_s / (p_n * 10 ** (snr_db / 10.0)))
+    if kind == "step":
+        g_db = np.where(np.arange(n) >= int(at * n), float(change_db), 0.0)
+    else:
+        g_db = float(change_db) * np.arange(n) / n
+    noisy = np.clip(clean + noise * 10 ** (g_db / 20.0), -1.0, 1.0) + 1e-6 * rng.standard_normal(n)
     return clean, noisy
 
 
