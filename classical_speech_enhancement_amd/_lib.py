@@ -120,17 +120,15 @@ EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_stoi_cells_sr")
 # include/cse_estoi.h (extended STOI), a header of its own: EXPORTS is what cse.h declares
 EXPORTS_ESTOI = ("cse_estoi_workspace_bytes", "cse_estoi_prepare", "cse_estoi_cells")
-# include/cse_mcra.h (MCRA noise tracking), likewise
-EXPORTS_MCRA = ("cse_mcra_default_params", "cse_noise_mcra")
 # include/cse_segsnr.h (segmental and frequency-weighted segmental SNR), likewise
 EXPORTS_SEGSNR = ("cse_segsnr_workspace_bytes", "cse_segsnr_prepare", "cse_segsnr_scratch_bytes",
                   "cse_segsnr_cells")
-# include/cse_spp.h (SPP-MMSE noise tracking), likewise
-EXPORTS_SPP = ("cse_spp_default_params", "cse_noise_spp")
-# include/cse_minstat.h (minimum-statistics noise tracking), likewise
-EXPORTS_MINSTAT = ("cse_minstat_default_params", "cse_noise_minstat")
-# include/cse_imcra.h (IMCRA noise tracking), likewise
-EXPORTS_IMCRA = ("cse_imcra_default_params", "cse_noise_imcra")
+# the noise trackers (NOISE's methods after the reference's three), each with a
+# header of its own, include/cse_<name>.h: name -> (default-parameters entry,
+# estimate entry); the four names are what the per-tracker tests read
+TRACKER_EXPORTS = {t: (f"cse_{t}_default_params", f"cse_noise_{t}")
+                   for t, code in NOISE.items() if code > 2}
+EXPORTS_MCRA, EXPORTS_SPP, EXPORTS_MINSTAT, EXPORTS_IMCRA = TRACKER_EXPORTS.values()
 # include/cse_lpc.h (log-likelihood ratio and LPC cepstrum distance), likewise
 EXPORTS_LPC = ("cse_lpc_workspace_bytes", "cse_lpc_prepare", "cse_lpc_scratch_bytes",
                "cse_lpc_cells")
@@ -229,22 +227,11 @@ def load(path=LIB_PATH):
     lib.cse_estoi_prepare.argtypes = [P, i64, i64, i32, P, P]
     lib.cse_estoi_cells.restype = i32
     lib.cse_estoi_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
-    lib.cse_mcra_default_params.restype = None
-    lib.cse_mcra_default_params.argtypes = [P]
-    lib.cse_noise_mcra.restype = i32
-    lib.cse_noise_mcra.argtypes = [P, i64, i32, i32, P, f64, P, P]
-    lib.cse_spp_default_params.restype = None
-    lib.cse_spp_default_params.argtypes = [P]
-    lib.cse_noise_spp.restype = i32
-    lib.cse_noise_spp.argtypes = [P, i64, i32, i32, P, f64, P, P]
-    lib.cse_minstat_default_params.restype = None
-    lib.cse_minstat_default_params.argtypes = [P]
-    lib.cse_noise_minstat.restype = i32
-    lib.cse_noise_minstat.argtypes = [P, i64, i32, i32, P, f64, P, P]
-    lib.cse_imcra_default_params.restype = None
-    lib.cse_imcra_default_params.argtypes = [P]
-    lib.cse_noise_imcra.restype = i32
-    lib.cse_noise_imcra.argtypes = [P, i64, i32, i32, P, f64, P, P]
+    for default_entry, entry in TRACKER_EXPORTS.values():
+        getattr(lib, default_entry).restype = None
+        getattr(lib, default_entry).argtypes = [P]
+        getattr(lib, entry).restype = i32
+        getattr(lib, entry).argtypes = [P, i64, i32, i32, P, f64, P, P]
     lib.cse_segsnr_workspace_bytes.restype = i64
     lib.cse_segsnr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_segsnr_prepare.restype = i32

@@ -18,14 +18,12 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, trackers
 # the planning names other modules and the tests import from here stay importable
 from .layout import (ALGO_COST, ALGOS, ALIGN_CORR_SAMPLES, ALIGN_MAX_LAG,  # noqa: F401
-                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, IMCRA_DEFAULTS, MAIN, MCRA_DEFAULTS,
-                     MINSTAT_DEFAULTS, SHORT, SPP_DEFAULTS, PlanLayout, Ref, canonical_algo,
-                     imcra_params, imcra_values, mcra_params, mcra_values, minstat_params,
-                     minstat_values, n_frames, noise_key, noise_params, pack_waves, route,
-                     route_slots, specs_by_n_fft, spp_params, spp_values)
+                     ALIGN_MIN_SAMPLES, DEFAULTS, GENERIC, MAIN, SHORT, PlanLayout, Ref,
+                     canonical_algo, n_frames, noise_key, noise_params, pack_waves, route,
+                     route_slots, specs_by_n_fft)
 
 
 def _ptr(t):
@@ -76,64 +74,21 @@ class Engine:
         adaptive_short, window_size, smoothing_factor; noise_estimation.py:12-13,
         :60).  true_noise: P is the power of STFT(noisy - clean) over the
         shorter length, fit to ``frames`` (default T') frames (:149-153).
-        mcra: cse_noise_mcra (include/cse_mcra.h) -> [S, T, B] at any T; params
-        are alpha_s, alpha_d, alpha_p, delta, window_frames.
-        spp: cse_noise_spp (include/cse_spp.h) -> [S, T, B] at any T; params are
-        prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames.
-        minstat: cse_noise_minstat (include/cse_minstat.h) -> [S, T, B] at any T;
-        params are the names of layout.MINSTAT_DEFAULTS.
-        imcra: cse_noise_imcra (include/cse_imcra.h) -> [S, T, B] at any T;
-        params are the names of layout.IMCRA_DEFAULTS."""
+        A tracker (trackers.TRACKERS): its cse_noise_<method>
+        (include/cse_<method>.h) -> [S, T, B] at any T; params are the names of
+        its record's defaults."""
         S, Tp, B = P.shape
-        if method == "mcra":
+        if method in trackers.TRACKERS:
+            tracker = trackers.TRACKERS[method]
             if frames is not None and int(frames) != Tp:
                 raise ValueError("frames applies to true_noise only")
-            unknown = set(params) - set(MCRA_DEFAULTS)
-            if unknown:
-                raise TypeError(f"mcra takes no parameter {sorted(unknown)[0]!r}")
-            prm = mcra_params(mcra_values(params))
+            trackers.check_names(tracker, params)
+            prm = trackers.params(tracker, tracker.values(params))
             if out is None:
                 out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
-            _lib.check(self.lib.cse_noise_mcra(_ptr(P), S, Tp, B, ctypes.byref(prm), float(eps),
-                                               _ptr(out), _stream()), "cse_noise_mcra")
-            return out
-        if method == "spp":
-            if frames is not None and int(frames) != Tp:
-                raise ValueError("frames applies to true_noise only")
-            unknown = set(params) - set(SPP_DEFAULTS)
-            if unknown:
-                raise TypeError(f"spp takes no parameter {sorted(unknown)[0]!r}")
-            prm = spp_params(spp_values(params))
-            if out is None:
-                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
-            _lib.check(self.lib.cse_noise_spp(_ptr(P), S, Tp, B, ctypes.byref(prm), float(eps),
-                                              _ptr(out), _stream()), "cse_noise_spp")
-            return out
-        if method == "minstat":
-            if frames is not None and int(frames) != Tp:
-                raise ValueError("frames applies to true_noise only")
-            unknown = set(params) - set(MINSTAT_DEFAULTS)
-            if unknown:
-                raise TypeError(f"minstat takes no parameter {sorted(unknown)[0]!r}")
-            prm = minstat_params(minstat_values(params))
-            if out is None:
-                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
-            _lib.check(self.lib.cse_noise_minstat(_ptr(P), S, Tp, B, ctypes.byref(prm),
-                                                  float(eps), _ptr(out), _stream()),
-                       "cse_noise_minstat")
-            return out
-        if method == "imcra":
-            if frames is not None and int(frames) != Tp:
-                raise ValueError("frames applies to true_noise only")
-            unknown = set(params) - set(IMCRA_DEFAULTS)
-            if unknown:
-                raise TypeError(f"imcra takes no parameter {sorted(unknown)[0]!r}")
-            prm = imcra_params(imcra_values(params))
-            if out is None:
-                out = torch.empty((S, Tp, B), dtype=torch.float32, device=P.device)
-            _lib.check(self.lib.cse_noise_imcra(_ptr(P), S, Tp, B, ctypes.byref(prm),
-                                                float(eps), _ptr(out), _stream()),
-                       "cse_noise_imcra")
+            _lib.check(getattr(self.lib, tracker.entry)(_ptr(P), S, Tp, B, ctypes.byref(prm),
+                                                        float(eps), _ptr(out), _stream()),
+                       tracker.entry)
             return out
         T = Tp if frames is None else int(frames)
         code = {"percentile": 0, "min_tracking": 1, "true_noise": 2, "simple": 0}[method]

@@ -13,7 +13,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, trackers
 
 # algorithm name (registry names of speech_enhancement_comparison.py:395-401)
 # -> (code, eps the reference passes to noise_estimation, param order in cse_cell_t)
@@ -68,243 +68,26 @@ def n_frames(length, hop):
     return 1 + int(length) // int(hop)
 
 
-# the MCRA tracker's parameters (include/cse_mcra.h; Cohen & Berdugo 2002, the
-# paper's values for n_fft 512 / hop 128 at 16 kHz).  Cell params carry them
-# as mcra_<name>.
-MCRA_DEFAULTS = {"alpha_s": 0.8, "alpha_d": 0.95, "alpha_p": 0.2, "delta": 5.0,
-                 "window_frames": 125}
-
-
-def mcra_values(params, prefix=""):
-    """(alpha_s, alpha_d, alpha_p, delta, window_frames) read from ``params``
-    under prefix + name, defaults where absent; raises ValueError for what
-    cse_noise_mcra refuses."""
-    a_s, a_d, a_p, delta = (float(params.get(prefix + k, MCRA_DEFAULTS[k]))
-                            for k in ("alpha_s", "alpha_d", "alpha_p", "delta"))
-    w = params.get(prefix + "window_frames", MCRA_DEFAULTS["window_frames"])
-    for name, a in (("alpha_s", a_s), ("alpha_d", a_d), ("alpha_p", a_p)):
-        if not 0.0 <= a < 1.0:
-            raise ValueError(f"mcra {name}={a} not in [0, 1)")
-    if not delta > 0.0:
-        raise ValueError(f"mcra delta={delta} not > 0")
-    if w != int(w) or not 2 <= int(w) < 2**31:
-        raise ValueError(f"mcra window_frames={w} not an integer >= 2")
-    return (a_s, a_d, a_p, delta, int(w))
-
-
-def mcra_params(values):
-    """cse_mcra_params_t from mcra_values' tuple."""
-    prm = _lib.McraParams()
-    prm.alpha_s, prm.alpha_d, prm.alpha_p, prm.delta, prm.window_frames = values
-    return prm
-
-
-# the SPP-MMSE tracker's parameters (include/cse_spp.h; Gerkmann & Hendriks 2012,
-# the paper's values).  Cell params carry them as spp_<name>.
-SPP_DEFAULTS = {"prior_h1": 0.5, "xi_opt_db": 15.0, "alpha_pow": 0.8, "alpha_ph": 0.9,
-                "ph_max": 0.99, "init_frames": 5}
-
-
-def spp_values(params, prefix=""):
-    """(prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max, init_frames) read from
-    ``params`` under prefix + name, defaults where absent; raises ValueError for
-    what cse_noise_spp refuses, and for an init_frames that is no integer."""
-    prior, xi, a_pow, a_ph, ph_max = (float(params.get(prefix + k, SPP_DEFAULTS[k]))
-                                      for k in ("prior_h1", "xi_opt_db", "alpha_pow", "alpha_ph",
-                                                "ph_max"))
-    k = params.get(prefix + "init_frames", SPP_DEFAULTS["init_frames"])
-    for name, v in (("prior_h1", prior), ("ph_max", ph_max)):
-        if not 0.0 < v < 1.0:
-            raise ValueError(f"spp {name}={v} not in (0, 1)")
-    for name, a in (("alpha_pow", a_pow), ("alpha_ph", a_ph)):
-        if not 0.0 <= a < 1.0:
-            raise ValueError(f"spp {name}={a} not in [0, 1)")
-    if not math.isfinite(xi):
-        raise ValueError(f"spp xi_opt_db={xi} not finite")
-    if not (isinstance(k, (int, float, np.integer, np.floating)) and math.isfinite(k)
-            and k == int(k) and 1 <= int(k) < 2**31):
-        raise ValueError(f"spp init_frames={k} not an integer >= 1")
-    return (prior, xi, a_pow, a_ph, ph_max, int(k))
-
-
-def spp_params(values):
-    """cse_spp_params_t from spp_values' tuple."""
-    prm = _lib.SppParams()
-    (prm.prior_h1, prm.xi_opt_db, prm.alpha_pow, prm.alpha_ph, prm.ph_max,
-     prm.init_frames) = values
-    return prm
-
-
-# the minimum-statistics tracker's parameters (include/cse_minstat.h; Martin
-# 2001, the paper's time constants at an 8-ms frame step: hop 128 at 16 kHz).
-# Cell params carry them as minstat_<name>.
-MINSTAT_DEFAULTS = {"alpha_c": 0.837, "alpha_c_floor": 0.7, "alpha_max": 0.98, "alpha_min": 0.548,
-                    "snr_exp": -0.125, "beta_max": 0.894, "av": 2.12, "q_eq_min": 2.0,
-                    "q_eq_max": 14.0, "slope_q": (0.03, 0.05, 0.06),
-                    "slope_max": (8.0, 4.0, 2.0, 1.2), "sub_windows": 8, "sub_frames": 24}
-_MINSTAT_SCALARS = ("alpha_c", "alpha_c_floor", "alpha_max", "alpha_min", "snr_exp", "beta_max",
-                    "av", "q_eq_min", "q_eq_max")
-
-
-def _whole(v, lo, hi):
-    return (isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
-            and v == int(v) and lo <= int(v) <= hi)
-
-
-def minstat_values(params, prefix=""):
-    """(alpha_c, alpha_c_floor, alpha_max, alpha_min, snr_exp, beta_max, av,
-    q_eq_min, q_eq_max, slope_q, slope_max, sub_windows, sub_frames) read from
-    ``params`` under prefix + name, defaults where absent, slope_q and slope_max
-    as tuples; raises ValueError for what cse_noise_minstat refuses, and for
-    sub_windows / sub_frames that are no integers."""
-    get = lambda k: params.get(prefix + k, MINSTAT_DEFAULTS[k])  # noqa: E731
-    v = {k: float(get(k)) for k in _MINSTAT_SCALARS}
-    for k, n in (("slope_q", 3), ("slope_max", 4)):
-        try:
-            v[k] = tuple(float(x) for x in get(k))
-        except TypeError:
-            v[k] = ()
-        if len(v[k]) != n:
-            raise ValueError(f"minstat {k}={get(k)!r} not {n} numbers")
-    for k in ("alpha_c", "alpha_c_floor", "alpha_min", "beta_max"):
-        if not 0.0 <= v[k] < 1.0:
-            raise ValueError(f"minstat {k}={v[k]} not in [0, 1)")
-    if not 0.0 < v["alpha_max"] < 1.0:
-        raise ValueError(f"minstat alpha_max={v['alpha_max']} not in (0, 1)")
-    if not (math.isfinite(v["snr_exp"]) and v["snr_exp"] <= 0.0):
-        raise ValueError(f"minstat snr_exp={v['snr_exp']} not finite or > 0")
-    if not (math.isfinite(v["av"]) and v["av"] >= 0.0):
-        raise ValueError(f"minstat av={v['av']} not finite or < 0")
-    if not 2.0 <= v["q_eq_min"] <= v["q_eq_max"] < math.inf:
-        raise ValueError(f"minstat not 2 <= q_eq_min={v['q_eq_min']} <= "
-                         f"q_eq_max={v['q_eq_max']} < inf")
-    q = v["slope_q"]
-    if not (0.0 < q[0] < q[1] < q[2] < math.inf):
-        raise ValueError(f"minstat slope_q={q} not positive and strictly increasing")
-    if not all(math.isfinite(x) and x >= 1.0 for x in v["slope_max"]):
-        raise ValueError(f"minstat slope_max={v['slope_max']} not all finite and >= 1")
-    U, V = get("sub_windows"), get("sub_frames")
-    if not _whole(U, 1, 16):
-        raise ValueError(f"minstat sub_windows={U} not an integer in [1, 16]")
-    if not _whole(V, 2, 2**20):
-        raise ValueError(f"minstat sub_frames={V} not an integer in [2, 2^20]")
-    return tuple(v[k] for k in _MINSTAT_SCALARS) + (v["slope_q"], v["slope_max"], int(U), int(V))
-
-
-def minstat_params(values):
-    """cse_minstat_params_t from minstat_values' tuple."""
-    prm = _lib.MinstatParams()
-    for k, x in zip(_MINSTAT_SCALARS, values):
-        setattr(prm, k, x)
-    prm.slope_q[:] = values[9]
-    prm.slope_max[:] = values[10]
-    prm.sub_windows, prm.sub_frames = values[11], values[12]
-    return prm
-
-
-def minstat_time_constants(hop_length, sr):
-    """The parameter dict for a frame step of hop_length / sr seconds, from the
-    time constants behind MINSTAT_DEFAULTS (which are this at 128 / 16000):
-    alpha = exp(-step / tau), snr_exp = -step / 0.064, the sub-window's 0.192 s
-    in frames (at least 2), U = 8.  The thresholds on the degrees of freedom and
-    slope_max stay.  The plugins do not call it on their own."""
-    step = float(hop_length) / float(sr)
-    if not (step > 0.0 and math.isfinite(step)):
-        raise ValueError(f"hop_length={hop_length} sr={sr}: no frame step")
-    tau = {"alpha_c": 0.0449, "alpha_max": 0.392, "alpha_min": 0.0133, "beta_max": 0.0717}
-    out = dict(MINSTAT_DEFAULTS)
-    out.update((k, math.exp(-step / t)) for k, t in tau.items())
-    out["snr_exp"] = -step / 0.064
-    out["sub_windows"] = 8
-    out["sub_frames"] = max(2, int(round(0.192 / step)))
-    return out
-
-
-# the IMCRA tracker's parameters (include/cse_imcra.h; Cohen 2003, the paper's
-# values for n_fft 512 / hop 128 at 16 kHz).  Cell params carry them as
-# imcra_<name>.
-IMCRA_DEFAULTS = {"alpha": 0.92, "alpha_s": 0.9, "alpha_d": 0.85, "beta": 1.47, "b_min": 1.66,
-                  "gamma0": 4.6, "gamma1": 3.0, "zeta0": 1.67, "xi_min_db": -18.0,
-                  "sub_windows": 8, "sub_frames": 15}
-_IMCRA_SCALARS = ("alpha", "alpha_s", "alpha_d", "beta", "b_min", "gamma0", "gamma1", "zeta0",
-                  "xi_min_db")
-
-
-def imcra_values(params, prefix=""):
-    """(alpha, alpha_s, alpha_d, beta, b_min, gamma0, gamma1, zeta0, xi_min_db,
-    sub_windows, sub_frames) read from ``params`` under prefix + name, defaults
-    where absent; raises ValueError for what cse_noise_imcra refuses, and for
-    sub_windows / sub_frames that are no integers."""
-    get = lambda k: params.get(prefix + k, IMCRA_DEFAULTS[k])  # noqa: E731
-    v = {k: float(get(k)) for k in _IMCRA_SCALARS}
-    for k in ("alpha", "alpha_s", "alpha_d"):
-        if not 0.0 <= v[k] < 1.0:
-            raise ValueError(f"imcra {k}={v[k]} not in [0, 1)")
-    for k in ("beta", "b_min", "gamma0", "zeta0"):
-        if not 0.0 < v[k] < math.inf:
-            raise ValueError(f"imcra {k}={v[k]} not finite and > 0")
-    if not 1.0 < v["gamma1"] < math.inf:
-        raise ValueError(f"imcra gamma1={v['gamma1']} not finite and > 1")
-    if not math.isfinite(v["xi_min_db"]):
-        raise ValueError(f"imcra xi_min_db={v['xi_min_db']} not finite")
-    U, V = get("sub_windows"), get("sub_frames")
-    if not _whole(U, 1, 16):
-        raise ValueError(f"imcra sub_windows={U} not an integer in [1, 16]")
-    if not _whole(V, 1, 2**20):
-        raise ValueError(f"imcra sub_frames={V} not an integer in [1, 2^20]")
-    return tuple(v[k] for k in _IMCRA_SCALARS) + (int(U), int(V))
-
-
-def imcra_params(values):
-    """cse_imcra_params_t from imcra_values' tuple."""
-    prm = _lib.ImcraParams()
-    for k, x in zip(_IMCRA_SCALARS + ("sub_windows", "sub_frames"), values):
-        setattr(prm, k, x)
-    return prm
-
-
-def imcra_time_constants(hop_length, sr):
-    """The parameter dict for a frame step of hop_length / sr seconds, from the
-    time constants behind IMCRA_DEFAULTS (which are this at 128 / 16000, exactly):
-    alpha, alpha_s and alpha_d become exp(-step / tau) with tau = -0.008 /
-    log(default), that is default ** (step / 0.008); the sub-window's 0.12 s in
-    frames (at least 1), U = 8.  beta, b_min and the thresholds stay.  The
-    plugins do not call it on their own."""
-    step = float(hop_length) / float(sr)
-    if not (step > 0.0 and math.isfinite(step)):
-        raise ValueError(f"hop_length={hop_length} sr={sr}: no frame step")
-    out = dict(IMCRA_DEFAULTS)
-    out.update((k, IMCRA_DEFAULTS[k] ** (step / 0.008)) for k in ("alpha", "alpha_s", "alpha_d"))
-    out["sub_windows"] = 8
-    out["sub_frames"] = max(1, int(math.floor(0.12 / step + 0.5)))
-    return out
-
-
-# the trackers that go beyond the reference: method -> (values function, params
-# function); their values tuple is the estimator slot of a noise key
-TRACKERS = {"mcra": (mcra_values, mcra_params), "spp": (spp_values, spp_params),
-            "minstat": (minstat_values, minstat_params)}
-# TRACKERS keeps the three names it was published with (callers and
-# tests/test_minstat_host.py compare its key set); the registry that noise keys
-# and call lists are built from is ALL_TRACKERS, which holds every tracker
-ALL_TRACKERS = dict(TRACKERS, imcra=(imcra_values, imcra_params))
-
-
-def tracker_values(params):
-    """The values tuple of a cell whose noise_method is a tracker (its
-    parameters read as <method>_<name>), () for every other method."""
-    method = params["noise_method"]
-    return ALL_TRACKERS[method][0](params, method + "_") if method in ALL_TRACKERS else ()
+# the trackers that go beyond the reference live in trackers.py; the names
+# callers and tests have imported from here stay importable
+TRACKERS = ALL_TRACKERS = trackers.TRACKERS
+tracker_values = trackers.tracker_values
+MCRA_DEFAULTS, SPP_DEFAULTS, MINSTAT_DEFAULTS, IMCRA_DEFAULTS = (
+    t.defaults for t in TRACKERS.values())
+mcra_values, spp_values, minstat_values, imcra_values = (t.values for t in TRACKERS.values())
+mcra_params, spp_params, minstat_params, imcra_params = (
+    (lambda values, t=t: trackers.params(t, values)) for t in TRACKERS.values())
+minstat_time_constants = TRACKERS["minstat"].time_constants
+imcra_time_constants = TRACKERS["imcra"].time_constants
 
 
 def noise_key(alg, params, T):
     """Which noise PSD array a cell reads, mirroring each algorithm's pipeline.
 
     Returns (method, pct, eps, expand, mu, inverse); pct is the estimator's
-    parameter slot: the percentile, or for mcra / spp / minstat / imcra the
-    mcra_values / spp_values / minstat_values / imcra_values tuple
-    (noise_percentile does not enter: cells that differ only in it share one
-    estimate):
+    parameter slot: the percentile, or for a tracker (trackers.TRACKERS) its
+    values tuple (noise_percentile does not enter: cells that differ only in
+    it share one estimate):
       - every algorithm estimates with the eps it passes (ss/wiener/omlsa 1e-10,
         mmse 1e-12: spectral_subtractor.py:17, wiener_filter.py:23, mmse.py:17,
         advanced_mmse.py:26);
@@ -315,9 +98,9 @@ def noise_key(alg, params, T):
         advanced_mmse.py:54-55), which ZERO-PADS frames 1..T-1 — frame 0 sees
         the estimate, later frames see 0 (SS) or, after OMLSA's smoothing,
         mu**t times it;
-      - mcra, spp, minstat and imcra (no counterpart in the reference) are
-        time-varying and take min_tracking's place in each pipeline: smoothed by mmse/omlsa, inverted
-        with the algorithm's eps for Wiener/MMSE/OMLSA, as they are for SS;
+      - the trackers (no counterpart in the reference) are time-varying and
+        take min_tracking's place in each pipeline: smoothed by mmse/omlsa,
+        inverted with the algorithm's eps for Wiener/MMSE/OMLSA, as they are for SS;
       - mmse/omlsa smooth any time-varying estimate except true_noise
         (mmse.py:48-54, advanced_mmse.py:60-66); mu=None means no smoothing;
       - inverse: Wiener/MMSE/OMLSA read 1/max(N, eps) (their in-loop floor,
@@ -587,9 +370,10 @@ class PlanLayout:
             if method == "simple":
                 calls.append(("cse_noise_estimate",
                               (0, P, S, T, B, 25.0, float(eps), raw(b), ws)))
-            elif method in ALL_TRACKERS:  # mcra, spp, ...: one call per (parameter set, eps)
-                calls.append(("cse_noise_" + method,
-                              (P, S, T, B, ALL_TRACKERS[method][1](pct), float(eps), raw(b))))
+            elif method in TRACKERS:  # one call per (parameter set, eps)
+                calls.append((TRACKERS[method].entry,
+                              (P, S, T, B, trackers.params(TRACKERS[method], pct), float(eps),
+                               raw(b))))
             elif method == "true_noise":
                 prm = noise_params(src_frames=self.ptrue_shape[hop][1])
                 calls.append(("cse_noise_estimate_ex",

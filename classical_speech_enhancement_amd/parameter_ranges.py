@@ -60,8 +60,9 @@ ALGORITHM_GRIDS = {
 
 def grids_with_noise_methods(methods, grids=None):
     """Copies of the grids (default ALGORITHM_GRIDS) with the noise_method axis
-    replaced by ``methods``, e.g. ("percentile", "min_tracking", "mcra", "spp",
-    "minstat", "imcra"): for search.job_specs / run_grid / run_sweep
+    replaced by ``methods``, e.g. ("percentile", "min_tracking") +
+    tuple(trackers.TRACKERS), the registry's "mcra" to "imcra", or any of
+    them: for search.job_specs / run_grid / run_sweep
     (grids=...).  The default grids, and so their cell ids, stay as they are."""
     methods = list(methods)
     if not methods:

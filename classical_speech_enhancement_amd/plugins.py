@@ -12,24 +12,18 @@ the device (fp64 analysis), within the 1e-5 relative tolerance of the
 north-star.  There is no CPU fallback: without the built library or a GPU
 these raise.
 
-One estimator goes beyond the reference: noise_method="mcra" (minima-controlled
-recursive averaging, include/cse_mcra.h).  The four algorithm plugins take its
-parameters as a trailing keyword mcra={alpha_s, alpha_d, alpha_p, delta,
-window_frames} (defaults: the paper's); every other call means what it meant.
-So does noise_method="spp" (SPP-based MMSE tracking, include/cse_spp.h), with
-the trailing keyword spp={prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max,
-init_frames}, and noise_method="minstat" (minimum statistics,
-include/cse_minstat.h), with the trailing keyword minstat={...} (the names of
-layout.MINSTAT_DEFAULTS; defaults: the paper's time constants at an 8-ms step),
-and noise_method="imcra" (improved MCRA, include/cse_imcra.h), with the trailing
-keyword imcra={...} (the names of layout.IMCRA_DEFAULTS; defaults: the paper's).
+The trackers of trackers.TRACKERS go beyond the reference: noise_method=<name>
+selects one (include/cse_<name>.h is its specification), and the four
+algorithm plugins take its parameters as a trailing keyword <name>={...} with
+the names of its record's defaults (the papers' values); every other call
+means what it meant.
 """
 
 import numpy as np
 import torch
 
-from .engine import (IMCRA_DEFAULTS, MCRA_DEFAULTS, MINSTAT_DEFAULTS, NOISE_PARAM_KEYS,
-                     SPP_DEFAULTS, Engine, n_frames)
+from .engine import NOISE_PARAM_KEYS, Engine, n_frames
+from .trackers import TRACKERS, check_names
 
 _ENGINE = None
 
@@ -55,27 +49,11 @@ def _dev(x):
     return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).cuda().view(1, -1)
 
 
-def _single(alg, noisy, clean, params, rule, mcra=None, spp=None, minstat=None, imcra=None):
-    if mcra:  # the tracker's parameters ride in the cell params as mcra_<name>
-        unknown = set(mcra) - set(MCRA_DEFAULTS)
-        if unknown:
-            raise TypeError(f"mcra takes no parameter {sorted(unknown)[0]!r}")
-        params.update(("mcra_" + k, v) for k, v in mcra.items())
-    if spp:  # likewise, as spp_<name>
-        unknown = set(spp) - set(SPP_DEFAULTS)
-        if unknown:
-            raise TypeError(f"spp takes no parameter {sorted(unknown)[0]!r}")
-        params.update(("spp_" + k, v) for k, v in spp.items())
-    if minstat:  # likewise, as minstat_<name>
-        unknown = set(minstat) - set(MINSTAT_DEFAULTS)
-        if unknown:
-            raise TypeError(f"minstat takes no parameter {sorted(unknown)[0]!r}")
-        params.update(("minstat_" + k, v) for k, v in minstat.items())
-    if imcra:  # likewise, as imcra_<name>
-        unknown = set(imcra) - set(IMCRA_DEFAULTS)
-        if unknown:
-            raise TypeError(f"imcra takes no parameter {sorted(unknown)[0]!r}")
-        params.update(("imcra_" + k, v) for k, v in imcra.items())
+def _single(alg, noisy, clean, params, rule, tracker_kw):
+    for name, given in tracker_kw.items():
+        if given:  # the tracker's parameters ride in the cell params as <name>_<parameter>
+            check_names(TRACKERS[name], given)
+            params.update((name + "_" + k, v) for k, v in given.items())
     x = _mono(noisy, rule)
     if x.size == 0:  # the reference's reflect padding of an empty signal raises
         raise ValueError("can't extend empty axis 0 using modes other than 'constant' or 'empty'")
@@ -105,7 +83,7 @@ def spectral_subtraction(noisy_audio, sr, alpha, beta, n_fft, hop_length, noise_
     return _single("spectralSubtractor", noisy_audio, clean_audio,
                    dict(alpha=alpha, beta=beta, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method),
-                   "shorter", mcra, spp, minstat, imcra)
+                   "shorter", dict(mcra=mcra, spp=spp, minstat=minstat, imcra=imcra))
 
 
 def wiener_filter(noisy_audio, sr, n_fft, hop_length, alpha, gain_floor, noise_percentile,
@@ -113,7 +91,7 @@ def wiener_filter(noisy_audio, sr, n_fft, hop_length, alpha, gain_floor, noise_p
     return _single("wiener", noisy_audio, clean_audio,
                    dict(alpha=alpha, gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method), "axis1",
-                   mcra, spp, minstat, imcra)
+                   dict(mcra=mcra, spp=spp, minstat=minstat, imcra=imcra))
 
 
 def mmse(noisy_audio, sr, alpha, ksi_min, gain_min, gain_max, n_fft, hop_length,
@@ -122,8 +100,8 @@ def mmse(noisy_audio, sr, alpha, ksi_min, gain_min, gain_max, n_fft, hop_length,
     return _single("mmse", noisy_audio, clean_audio,
                    dict(alpha=alpha, ksi_min=ksi_min, gain_min=gain_min, gain_max=gain_max,
                         n_fft=n_fft, hop_length=hop_length, noise_percentile=noise_percentile,
-                        noise_method=noise_method, noise_mu=noise_mu), "axis1", mcra,
-                   spp, minstat, imcra)
+                        noise_method=noise_method, noise_mu=noise_mu), "axis1",
+                   dict(mcra=mcra, spp=spp, minstat=minstat, imcra=imcra))
 
 
 def advanced_mmse(noisy_audio, sr, n_fft, hop_length, alpha, ksi_min, q, noise_mu, gain_floor,
@@ -133,7 +111,8 @@ def advanced_mmse(noisy_audio, sr, n_fft, hop_length, alpha, ksi_min, q, noise_m
                    dict(alpha=alpha, ksi_min=ksi_min, q=q, noise_mu=noise_mu,
                         gain_floor=gain_floor, n_fft=n_fft, hop_length=hop_length,
                         noise_percentile=noise_percentile, noise_method=noise_method,
-                        v_max=v_max), "shorter", mcra, spp, minstat, imcra)
+                        v_max=v_max), "shorter",
+                   dict(mcra=mcra, spp=spp, minstat=minstat, imcra=imcra))
 
 
 def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win_length=None,
@@ -148,13 +127,9 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
     eps defaults to 1e-10 (percentile, min_tracking) / 1e-12 (true_noise), the
     T < 5 fallback reads eps from the merged dict (:191-195).
 
-    method="mcra" (not in the reference; include/cse_mcra.h) returns (B,T):
-    alpha_s, alpha_d, alpha_p, delta and window_frames come from the merged
-    dict, eps from **kwargs (default 1e-10).  method="spp" (include/cse_spp.h)
-    likewise, with prior_h1, xi_opt_db, alpha_pow, alpha_ph, ph_max and
-    init_frames, method="minstat" (include/cse_minstat.h) with the names of
-    layout.MINSTAT_DEFAULTS and method="imcra" (include/cse_imcra.h) with those
-    of layout.IMCRA_DEFAULTS."""
+    A tracker (trackers.TRACKERS, not in the reference) returns (B,T): the
+    parameters named in its record's defaults come from the merged dict, eps
+    from **kwargs (default 1e-10)."""
     if window != "hann" or not center or pad_mode != "reflect" or (win_length or n_fft) != n_fft:
         raise NotImplementedError("only hann/center/reflect/win_length=n_fft is implemented")
     full = dict(estimator_params or {})
@@ -180,25 +155,10 @@ def noise_estimation(y, sr, method="percentile", n_fft=1024, hop_length=256, win
         _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
         N = eng.noise_estimate("min_tracking", P, eps=kwargs.get("eps", 1e-10), **ctor)
         return N[0].cpu().numpy().astype(np.float64).T
-    if method == "mcra":
+    if method in TRACKERS:
         _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
-        N = eng.noise_estimate("mcra", P, eps=kwargs.get("eps", 1e-10),
-                               **{k: full[k] for k in MCRA_DEFAULTS if k in full})
-        return N[0].cpu().numpy().astype(np.float64).T
-    if method == "spp":
-        _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
-        N = eng.noise_estimate("spp", P, eps=kwargs.get("eps", 1e-10),
-                               **{k: full[k] for k in SPP_DEFAULTS if k in full})
-        return N[0].cpu().numpy().astype(np.float64).T
-    if method == "minstat":
-        _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
-        N = eng.noise_estimate("minstat", P, eps=kwargs.get("eps", 1e-10),
-                               **{k: full[k] for k in MINSTAT_DEFAULTS if k in full})
-        return N[0].cpu().numpy().astype(np.float64).T
-    if method == "imcra":
-        _, P = eng.stft(xd, n_fft, hop_length, want_y=False)
-        N = eng.noise_estimate("imcra", P, eps=kwargs.get("eps", 1e-10),
-                               **{k: full[k] for k in IMCRA_DEFAULTS if k in full})
+        N = eng.noise_estimate(method, P, eps=kwargs.get("eps", 1e-10),
+                               **{k: full[k] for k in TRACKERS[method].defaults if k in full})
         return N[0].cpu().numpy().astype(np.float64).T
     if method == "true_noise":
         clean = kwargs.get("clean_audio")

@@ -76,6 +76,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .parameter_ranges import ALGORITHM_GRIDS, grid_cells
+from .trackers import TRACKERS
 
 # per-bin cost weights (measured kernel time per frame, OMLSA ~ 3x SS)
 ALGO_WEIGHT = {"spectralSubtractor": 1.0, "wiener": 1.1, "mmse": 2.0, "omlsa": 3.0}
@@ -750,7 +751,7 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     return table, select_best(specs, table, objective)
 
 
-NOISE_METHODS = ("percentile", "min_tracking", "true_noise", "mcra", "spp", "minstat", "imcra")
+NOISE_METHODS = ("percentile", "min_tracking", "true_noise") + tuple(TRACKERS)
 # bound on the noise-PSD estimates score_noise_estimators holds at once (f32
 # bytes): 4 GiB, 32 estimates of 100 10-s pairs at n_fft 512 / hop 128
 NOISE_EST_BYTES = 4 << 30

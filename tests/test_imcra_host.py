@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import _imcra_ref
-from classical_speech_enhancement_amd import _lib, layout, parameter_ranges, search
+from classical_speech_enhancement_amd import _lib, layout, parameter_ranges, search, trackers
 
 HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "cse_imcra.h")
 SCALARS = ("alpha", "alpha_s", "alpha_d", "beta", "b_min", "gamma0", "gamma1", "zeta0",
@@ -229,9 +229,10 @@ def test_imcra_values_is_hashable_and_reads_the_prefix():
     assert hash(v) == hash(tuple(v)) and isinstance(v[10], int) and isinstance(v[6], float)
     prm = layout.imcra_params(v)
     assert isinstance(prm, _lib.ImcraParams) and _as_tuple(prm) == v
-    assert layout.ALL_TRACKERS["imcra"] == (layout.imcra_values, layout.imcra_params)
-    assert set(layout.ALL_TRACKERS) >= set(layout.TRACKERS) | {"imcra"}
-    assert all(layout.ALL_TRACKERS[k] == v for k, v in layout.TRACKERS.items())
+    assert tuple(layout.TRACKERS) == ("mcra", "spp", "minstat", "imcra")
+    assert layout.TRACKERS["imcra"].values is layout.imcra_values
+    assert bytes(trackers.params(layout.TRACKERS["imcra"], v)) == bytes(layout.imcra_params(v))
+    assert layout.ALL_TRACKERS is layout.TRACKERS
     assert layout.tracker_values({"noise_method": "imcra", "imcra_beta": 1.2}) == \
         DEFAULT_VALUES[:3] + (1.2,) + DEFAULT_VALUES[4:]
     assert layout.tracker_values({"noise_method": "imcra"}) == DEFAULT_VALUES

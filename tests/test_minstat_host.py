@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import _minstat_ref
-from classical_speech_enhancement_amd import _lib, layout, parameter_ranges, search
+from classical_speech_enhancement_amd import _lib, layout, parameter_ranges, search, trackers
 
 HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "cse_minstat.h")
 SCALARS = ("alpha_c", "alpha_c_floor", "alpha_max", "alpha_min", "snr_exp", "beta_max", "av",
@@ -231,8 +231,9 @@ def test_minstat_values_is_hashable_and_reads_the_prefix():
     assert hash(v) == hash(tuple(v)) and isinstance(v[9], tuple) and isinstance(v[12], int)
     prm = layout.minstat_params(v)
     assert isinstance(prm, _lib.MinstatParams) and _as_tuple(prm) == v
-    assert set(layout.TRACKERS) == {"mcra", "spp", "minstat"}
-    assert layout.TRACKERS["minstat"] == (layout.minstat_values, layout.minstat_params)
+    assert tuple(layout.TRACKERS) == ("mcra", "spp", "minstat", "imcra")
+    assert layout.TRACKERS["minstat"].values is layout.minstat_values
+    assert bytes(trackers.params(layout.TRACKERS["minstat"], v)) == bytes(layout.minstat_params(v))
 
 
 def _cell(alg, method, hop=128, pct=20.0, **extra):
