@@ -1,7 +1,7 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
-include/cse_sisdr.h and include/cse_logerr.h).
+include/cse_wss.h, include/cse_sisdr.h and include/cse_logerr.h).
 
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
@@ -132,6 +132,9 @@ EXPORTS_MCRA, EXPORTS_SPP, EXPORTS_MINSTAT, EXPORTS_IMCRA = TRACKER_EXPORTS.valu
 # include/cse_lpc.h (log-likelihood ratio and LPC cepstrum distance), likewise
 EXPORTS_LPC = ("cse_lpc_workspace_bytes", "cse_lpc_prepare", "cse_lpc_scratch_bytes",
                "cse_lpc_cells")
+# include/cse_wss.h (weighted spectral slope distance), likewise
+EXPORTS_WSS = ("cse_wss_workspace_bytes", "cse_wss_prepare", "cse_wss_scratch_bytes",
+               "cse_wss_cells")
 # include/cse_sisdr.h (SI-SDR, SI-SIR and SI-SAR), likewise
 EXPORTS_SISDR = ("cse_sisdr_workspace_bytes", "cse_sisdr_prepare", "cse_sisdr_scratch_bytes",
                  "cse_sisdr_cells")
@@ -248,6 +251,14 @@ def load(path=LIB_PATH):
     lib.cse_lpc_scratch_bytes.argtypes = [i64, i64, i32]
     lib.cse_lpc_cells.restype = i32
     lib.cse_lpc_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P, P]
+    lib.cse_wss_workspace_bytes.restype = i64
+    lib.cse_wss_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cse_wss_prepare.restype = i32
+    lib.cse_wss_prepare.argtypes = [P, i64, i64, i32, P, P]
+    lib.cse_wss_scratch_bytes.restype = i64
+    lib.cse_wss_scratch_bytes.argtypes = [i64, i64, i32]
+    lib.cse_wss_cells.restype = i32
+    lib.cse_wss_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
     lib.cse_sisdr_workspace_bytes.restype = i64
     lib.cse_sisdr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_sisdr_prepare.restype = i32

@@ -37,6 +37,12 @@ LpcPlan scores the two envelope-distortion measures of include/cse_lpc.h, the
 log-likelihood ratio and the LPC cepstrum distance (lower is better), through
 the same interface (cse_lpc_prepare / cse_lpc_cells).
 
+WssPlan scores the weighted spectral slope distance of include/cse_wss.h (Klatt
+1982; lower is better) the same way, one score per cell (cse_wss_prepare /
+cse_wss_cells).  With it the device delivers every ingredient of Hu & Loizou's
+composite measures but PESQ: composite() takes the caller's PESQ values with
+LLR, WSS and segSNR and returns CSIG, CBAK and COVL.
+
 SiSdrPlan scores the scale-invariant SDR of include/cse_sisdr.h (Le Roux et al.
 2019) and, when the batch's noisy signals are given, its split into SI-SIR
 (residual interference) and SI-SAR (artifacts) through cse_sisdr_prepare /
@@ -248,6 +254,30 @@ class SegSnrPlan:
         first, second = self._WHICH
         if which not in ("both", first, second):
             raise ValueError(f"which={which!r}: 'both', {first!r} or {second!r}")
+        off, sig, lg, n = self._cell_index(y, y_offset, sig_of, lag)
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        if out.shape != (n, 2) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n, 2] float64 tensor")
+        # the library writes one column each: planar scratch rows, then one copy
+        cols = torch.full((2, n), float("nan"), dtype=torch.float64, device=dev)
+        step = self.cells_per_launch()
+        for s in range(0, n, step):
+            m = min(step, n - s)
+            scratch = self._scratch_for(m)
+            _lib.check(self._fn("cells")(
+                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
+                self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
+                None if scratch is None else _ptr(scratch),
+                None if which == second else _ptr(cols[0, s:]),
+                None if which == first else _ptr(cols[1, s:]), _stream()), f"{self._PREFIX}_cells")
+        out.copy_(cols.t())
+        return out
+
+    def _cell_index(self, y, y_offset, sig_of, lag):
+        """score_async's checks of y and the index arrays: (y_offset, sig_of, lag
+        or None) on the device, and the number of cells."""
+        dev = self.clean.device
         if y.dtype != torch.float32 or not y.is_cuda:
             raise ValueError("y must be a float32 cuda tensor")
         if torch.is_tensor(y_offset):
@@ -285,24 +315,7 @@ class SegSnrPlan:
                 lg = torch.as_tensor(np.asarray(lag, dtype=np.int32), device=dev)
             if int(lg.numel()) != n:
                 raise ValueError("lag and y_offset differ in length")
-        if out is None:
-            out = torch.empty((n, 2), dtype=torch.float64, device=dev)
-        if out.shape != (n, 2) or out.dtype != torch.float64 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous [n, 2] float64 tensor")
-        # the library writes one column each: planar scratch rows, then one copy
-        cols = torch.full((2, n), float("nan"), dtype=torch.float64, device=dev)
-        step = self.cells_per_launch()
-        for s in range(0, n, step):
-            m = min(step, n - s)
-            scratch = self._scratch_for(m)
-            _lib.check(self._fn("cells")(
-                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
-                self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
-                None if scratch is None else _ptr(scratch),
-                None if which == second else _ptr(cols[0, s:]),
-                None if which == first else _ptr(cols[1, s:]), _stream()), f"{self._PREFIX}_cells")
-        out.copy_(cols.t())
-        return out
+        return off, sig, lg, n
 
     def score(self, y, y_offset, sig_of, lag=None, clip=True, which="both"):
         """score_async, synchronised: [n, 2] numpy (segsnr, fwsegsnr); NaN: no
@@ -321,6 +334,42 @@ class LpcPlan(SegSnrPlan):
     _PREFIX = "cse_lpc"
     _LABEL = "LLR/CEP"
     _WHICH = ("llr", "cep")
+
+
+class WssPlan(SegSnrPlan):
+    """Clean side of the weighted spectral slope distance (include/cse_wss.h) for
+    S equal-length signals at 16 or 8 kHz: SegSnrPlan's construction, checks and
+    launch chunking on cse_wss_prepare / cse_wss_cells, with one score per cell
+    (lower is better).  Clips of more than 1536 frames (11.5 s) select through
+    scratch the library sizes."""
+
+    _PREFIX = "cse_wss"
+    _LABEL = "WSS"
+    _WHICH = ("wss",)
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True, out=None):
+        """Enqueue the score of every cell; returns the [n] f64 cuda result.  The
+        arguments are SegSnrPlan.score_async's."""
+        off, sig, lg, n = self._cell_index(y, y_offset, sig_of, lag)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=self.clean.device)
+        if out.shape != (n,) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n] float64 tensor")
+        step = self.cells_per_launch()
+        for s in range(0, n, step):
+            m = min(step, n - s)
+            scratch = self._scratch_for(m)
+            _lib.check(self._fn("cells")(
+                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
+                self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
+                None if scratch is None else _ptr(scratch), _ptr(out[s:]), _stream()),
+                f"{self._PREFIX}_cells")
+        return out
+
+    def score(self, y, y_offset, sig_of, lag=None, clip=True):
+        """score_async, synchronised: [n] numpy; NaN: no frame, or no non-silent
+        frame."""
+        return self.score_async(y, y_offset, sig_of, lag, clip).cpu().numpy()
 
 
 class SiSdrPlan:
@@ -614,6 +663,45 @@ def cepstrum_distance(x, y, fs):
     return _plan_pair(LpcPlan, x, y, fs, "cep")
 
 
+def wss(x, y, fs):
+    """Weighted spectral slope distance (include/cse_wss.h) of y against the clean
+    x; lower is better."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if x.shape != y.shape:
+        raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
+    if x.ndim != 1 or x.size == 0:
+        raise ValueError("wss expects non-empty 1-D signals")
+    plan = WssPlan(torch.as_tensor(x).cuda().view(1, -1), fs)
+    v = float(plan.score(torch.as_tensor(y.astype(np.float32)).cuda(), [0], [0], clip=False)[0])
+    if math.isnan(v):
+        raise ValueError("no non-silent 30-ms frame")
+    return v
+
+
+def composite(pesq, llr, wss, segsnr):
+    """(CSIG, CBAK, COVL): Hu & Loizou's (2008) composite predictions of the
+    signal-distortion, background-intrusiveness and overall-quality ratings, the
+    regressions of Loizou's composite.m:
+
+        CSIG = 3.093 - 1.029 LLR + 0.603 PESQ - 0.009 WSS
+        CBAK = 1.634 + 0.478 PESQ - 0.007 WSS + 0.063 segSNR
+        COVL = 1.594 + 0.805 PESQ - 0.512 LLR - 0.007 WSS
+
+    each clamped to [1, 5].  Plain numpy on the host: the arguments broadcast
+    against each other and a NaN in one gives NaN in what depends on it.  pesq
+    is the caller's (ITU-T P.862 is not scored here); llr, wss and segsnr are
+    this project's variants (include/cse_lpc.h, cse_wss.h, cse_segsnr.h), which
+    leave exactly-silent clean frames out, so on clips with exact-zero pauses
+    the composites differ from composite.m's."""
+    pesq, llr, wss, segsnr = (np.asarray(v, dtype=np.float64) for v in (pesq, llr, wss, segsnr))
+    csig = 3.093 - 1.029 * llr + 0.603 * pesq - 0.009 * wss
+    cbak = 1.634 + 0.478 * pesq - 0.007 * wss + 0.063 * segsnr
+    covl = 1.594 + 0.805 * pesq - 0.512 * llr - 0.007 * wss
+    # np.clip keeps NaN
+    return tuple(np.clip(v, 1.0, 5.0)[()] for v in (csig, cbak, covl))
+
+
 def segsnr(x, y, fs):
     """Segmental SNR in dB (include/cse_segsnr.h) of y against the clean x."""
     return _segsnr_pair(x, y, fs, "segsnr")
@@ -653,6 +741,11 @@ def calculate_llr(clean_reference, test_audio, sr):
 def calculate_cep(clean_reference, test_audio, sr):
     """cepstrum_distance with calculate_stoi's shape: trim to the common length, None on failure."""
     return _calculate_quality(cepstrum_distance, "CEP", clean_reference, test_audio, sr)
+
+
+def calculate_wss(clean_reference, test_audio, sr):
+    """wss with calculate_stoi's shape: trim to the common length, None on failure."""
+    return _calculate_quality(wss, "WSS", clean_reference, test_audio, sr)
 
 
 def stoi(x, y, fs_sig, extended=False):
@@ -740,12 +833,13 @@ def _separation(clean_reference, noisy_audio, enhanced_audio):
 
 
 def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name="",
-                           quality=False, distortion=False, separation=False):
+                           quality=False, distortion=False, separation=False, wss=False):
     """evaluation_metrics.evaluate_audio_quality (:61-101), same keys;
     quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement);
     distortion=True adds llr_* and cep_* likewise, their improvement being
     noisy - enhanced (lower is better); separation=True adds sisdr_enhanced,
-    sisir_enhanced and sisar_enhanced, and sisdr_noisy with sisdr_improvement."""
+    sisir_enhanced and sisar_enhanced, and sisdr_noisy with sisdr_improvement;
+    wss=True adds wss_noisy, wss_enhanced and wss_improvement (noisy - enhanced)."""
     results = {}
     s_noisy = calculate_stoi(clean_reference, noisy_audio, sr)
     s_enh = calculate_stoi(clean_reference, enhanced_audio, sr)
@@ -780,6 +874,13 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
                 results[f"{key}_improvement"] = d_noisy - d_enh
     if separation:
         results.update(_separation(clean_reference, noisy_audio, enhanced_audio))
+    if wss:
+        w_noisy = calculate_wss(clean_reference, noisy_audio, sr)
+        w_enh = calculate_wss(clean_reference, enhanced_audio, sr)
+        if w_noisy is not None and w_enh is not None:
+            results["wss_noisy"] = w_noisy
+            results["wss_enhanced"] = w_enh
+            results["wss_improvement"] = w_noisy - w_enh
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:
@@ -793,6 +894,8 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     for key, label in (("llr", "LLR"), ("cep", "CEP")):
         if f"{key}_noisy" in results:
             print(f"{label}: {results[key + '_noisy']:.3f} -> {results[key + '_enhanced']:.3f}")
+    if "wss_noisy" in results:
+        print(f"WSS: {results['wss_noisy']:.2f} -> {results['wss_enhanced']:.2f}")
     if "sisdr_enhanced" in results:
         print(f"SI-SDR: {results['sisdr_noisy']:.2f} -> {results['sisdr_enhanced']:.2f} dB "
               f"(SI-SIR {results['sisir_enhanced']:.2f}, SI-SAR {results['sisar_enhanced']:.2f})")

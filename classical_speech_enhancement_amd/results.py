@@ -31,7 +31,8 @@ separation=True sweep does the same with sisdr_noisy and the SI-SDR-optimal
 cell's sisdr_best, sisir_sisdropt, sisar_sisdropt (the interference and artifact
 parts of its error), best_params_sisdr and snr_sisdropt.  There is no
 sisar_noisy: the unprocessed input's SI-SAR carries no meaning
-(include/cse_sisdr.h).
+(include/cse_sisdr.h).  A wss=True sweep does the same with wss_noisy and the
+WSS-optimal (lowest) cell's wss_best, best_params_wss and snr_wssopt.
 """
 
 import json
@@ -81,6 +82,12 @@ SEPARATION_SUMMARY_KEYS = (("sisdr_noisy_mean", "sisdr_noisy"), ("sisdr_best_mea
                            ("snr_sisdropt_mean", "snr_sisdropt"))
 
 
+WSS_ARGS = ("wss_noisy", "wss_best", "wss_params", "snr_wssopt")
+WSS_KEYS = ("wss_noisy", "wss_best", "best_params_wss", "snr_wssopt")
+WSS_SUMMARY_KEYS = (("wss_noisy_mean", "wss_noisy"), ("wss_best_mean", "wss_best"),
+                    ("snr_wssopt_mean", "snr_wssopt"))
+
+
 def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
                stoi_best=None, stoi_params=None, snr_stoiopt=None, **quality):
     """One all_results.json row (run_algorithm_on_pair :314-338).  STOI
@@ -93,14 +100,17 @@ def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
     snr_fwsegopt) add the QUALITY_KEYS of a quality=True sweep, the distortion
     keywords (all or none: DISTORTION_ARGS) the DISTORTION_KEYS of a
     distortion=True one, the separation keywords (all or none: SEPARATION_ARGS)
-    the SEPARATION_KEYS of a separation=True one."""
+    the SEPARATION_KEYS of a separation=True one, the WSS keywords (all or none,
+    and a part of them raises TypeError: WSS_ARGS) the WSS_KEYS of a wss=True
+    one."""
     row = {k: None for k in ROW_KEYS}
     row.update(alg=alg, stem=stem, sr=int(sr), snr_noisy=snr_noisy,
                best_params_stoi=dict(stoi_params or {}), best_params_pesq={},
                best_params_balanced={}, snr_snropt=best_snr,
                best_params_snr=dict(best_params or {}),
                stoi_noisy=stoi_noisy, stoi_stoiopt=stoi_best, snr_stoiopt=snr_stoiopt)
-    unknown = set(quality) - set(QUALITY_ARGS) - set(DISTORTION_ARGS) - set(SEPARATION_ARGS)
+    unknown = (set(quality) - set(QUALITY_ARGS) - set(DISTORTION_ARGS) - set(SEPARATION_ARGS)
+               - set(WSS_ARGS))
     if unknown:
         raise TypeError(f"result_row: unexpected keywords {sorted(unknown)}")
     if set(quality) & set(QUALITY_ARGS):
@@ -120,6 +130,14 @@ def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
                    sisar_sisdropt=quality.get("sisar_sisdropt"),
                    best_params_sisdr=dict(quality.get("sisdr_params") or {}),
                    snr_sisdropt=quality.get("snr_sisdropt"))
+    given = set(quality) & set(WSS_ARGS)
+    if given and given != set(WSS_ARGS):  # all or none: a lone key would leave a half-filled row
+        raise TypeError(f"result_row: the WSS keywords go together, missing "
+                        f"{sorted(set(WSS_ARGS) - given)}")
+    if given:
+        row.update(wss_noisy=quality.get("wss_noisy"), wss_best=quality.get("wss_best"),
+                   best_params_wss=dict(quality.get("wss_params") or {}),
+                   snr_wssopt=quality.get("snr_wssopt"))
     return row
 
 
@@ -147,6 +165,9 @@ def summary_means(all_results, algorithms):
                 entry[key] = safe_mean([r.get(field) for r in rows])
         if any("sisdr_best" in r for r in rows):  # a separation=True sweep
             for key, field in SEPARATION_SUMMARY_KEYS:
+                entry[key] = safe_mean([r.get(field) for r in rows])
+        if any("wss_best" in r for r in rows):  # a wss=True sweep
+            for key, field in WSS_SUMMARY_KEYS:
                 entry[key] = safe_mean([r.get(field) for r in rows])
         out[alg] = entry
     return out

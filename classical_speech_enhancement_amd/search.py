@@ -61,6 +61,12 @@ table that then always has NCOL + 7 columns, the quality and distortion columns
 NaN unless asked for too.  "sisdr", "sisir" and "sisar" are maximised; a value
 that is not finite (NaN, +inf, -inf) is skipped.
 
+wss=True (engine_compute, run_grid, run_sweep) adds the weighted spectral slope
+distance of include/cse_wss.h (cse_wss_cells), the one ingredient of Hu &
+Loizou's composite measures besides PESQ that the other columns do not hold:
+column NCOL + 7 (WSS_COLUMNS) of a table that then always has NCOL + 8 columns,
+the earlier optional columns NaN unless asked for too.  "wss" is minimised.
+
 score_noise_estimators and sweep_tracker judge noise-PSD estimates themselves,
 with no enhancement algorithm on top: the logarithmic estimation error of
 include/cse_logerr.h (cse_logerr_rows) against the smoothed power of the pair's
@@ -88,7 +94,10 @@ TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5,
              # sisdr / sisir / sisar (dB): the step of the other dB objectives
              "sisdr": 1e-3, "sisir": 1e-3, "sisar": 1e-3,
              # logerr (dB, sweep_tracker's objectives): the step of the other dB objectives
-             "logerr": 1e-3}
+             "logerr": 1e-3,
+             # wss: the PESQ step of 1e-3 on a 5-wide scale carried to a scale about 100 wide
+             # (2e-2), rounded down to a power of ten
+             "wss": 1e-2}
 
 # one float64 row per cell.  lag: finalize_enhanced's alignment lag (0 when
 # not aligned); xstatus: cse_xcorr_lag's status (engine: XCORR_OK, XCORR_FLAT =
@@ -102,7 +111,7 @@ QUALITY_COLUMNS = {"segsnr": 6, "fwsegsnr": 7}
 # where select_best's scan starts: the reference's -1 (speech_enhancement_comparison.py:126-141)
 # unless the objective's values go below it (dB scores clamped to [-10, 35])
 SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf, "llr": -math.inf, "cep": -math.inf,
-              "sisdr": -math.inf, "sisir": -math.inf, "sisar": -math.inf}
+              "sisdr": -math.inf, "sisir": -math.inf, "sisar": -math.inf, "wss": -math.inf}
 # distortion=True tables have NCOL + 4 columns: the two quality columns (NaN
 # without quality=True), then these.  Lower is better: select_best scans the
 # negated column
@@ -111,12 +120,17 @@ DISTORTION_COLUMNS = {"llr": 8, "cep": 9}
 # columns (NaN unless asked for too), then these.  Unbounded dB values that may
 # be +-inf or NaN (include/cse_sisdr.h): select_best skips what is not finite
 SEPARATION_COLUMNS = {"sisdr": NCOL + 4, "sisir": NCOL + 5, "sisar": NCOL + 6}
+# wss=True tables have NCOL + 8 columns: the quality, distortion and separation
+# columns (NaN unless asked for too), then this one.  Lower is better:
+# select_best scans the negated column
+WSS_COLUMNS = {"wss": NCOL + 7}
 
 
-def table_width(quality=False, distortion=False, separation=False):
+def table_width(quality=False, distortion=False, separation=False, wss=False):
     """Columns of a table: NCOL, + 2 with quality, + 4 with distortion (with or
-    without quality), + 7 with separation (whatever else is asked for)."""
-    return NCOL + (7 if separation else 4 if distortion else 2 if quality else 0)
+    without quality), + 7 with separation, + 8 with wss (whatever else is asked
+    for)."""
+    return NCOL + (8 if wss else 7 if separation else 4 if distortion else 2 if quality else 0)
 # bound on the cell waveforms held at once for STOI scoring (f32 bytes): 48 GiB
 # of the 288 GB HBM, i.e. 10 full 10-s pairs (7,308 computed cells x 640 KB each)
 # per batch, two batches in flight.  100-pair sweep (late r04, call_r04s.sh in profiles/r04_commands.md):
@@ -330,7 +344,7 @@ def _unique_inverse(x):
 
 
 def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True, quality=False,
-                   distortion=False, separation=False):
+                   distortion=False, separation=False, wss=False):
     """Device compute of the cells ``ids``: per-cell (sse, snr, finite, stoi,
     lag, xstatus), scored after finalize_enhanced's alignment (align=False: at
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
@@ -342,7 +356,9 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     are then there too, NaN unless quality=True.  separation=True makes the rows
     NCOL + 7 wide and fills sisdr, sisir and sisar (SEPARATION_COLUMNS), the
     interference being the pair's noisy - clean; the quality and distortion
-    columns are NaN unless asked for.
+    columns are NaN unless asked for.  wss=True makes the rows NCOL + 8 wide and
+    fills wss (WSS_COLUMNS) the same way, the earlier optional columns NaN unless
+    asked for.
 
     clean/noisy: lists of 1-D float arrays (host) indexed by pair.  Pairs are
     batched by length (the engine's signal batches are rectangular), and, when
@@ -366,7 +382,7 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     size0 = eng.plan_cache_size
     try:
         return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, bool(quality),
-                               bool(distortion), bool(separation))
+                               bool(distortion), bool(separation), bool(wss))
     finally:
         if own:
             eng._plan_cache.clear()
@@ -377,12 +393,12 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
 
 
 def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, distortion=False,
-                    separation=False):
+                    separation=False, wss=False):
     import torch
     from .engine import snr_db, spec_fingerprint, structure_digest
-    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan
+    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan, WssPlan
     # the cell waveforms are scored on the side stream
-    keep = bool(stoi) or quality or distortion or separation
+    keep = bool(stoi) or quality or distortion or separation or wss
     ids = np.asarray(ids, dtype=np.int64)
     lengths = [len(x) for x in noisy]
     js_specs = isinstance(specs, JobSpecs)
@@ -392,7 +408,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
     else:
         comp, back = ids, np.arange(len(ids))
         pair_of = np.fromiter((specs[c][0] for c in comp), dtype=np.int64, count=len(comp))
-    vals = np.full((len(comp), table_width(quality, distortion, separation)), np.nan)
+    vals = np.full((len(comp), table_width(quality, distortion, separation, wss)), np.nan)
     by_len = OrderedDict()
     upairs, first = np.unique(pair_of, return_index=True)
     for pair in upairs[np.argsort(first, kind="stable")].tolist():  # first-appearance order
@@ -410,10 +426,12 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
     nbatch = 0
 
     def collect(item):
-        rows_, fin_, out_, qout_, dout_, sout_, ev_, _refs = item
+        rows_, fin_, out_, qout_, dout_, sout_, wout_, ev_, _refs = item
         ev_.synchronize()
         if out_ is not None:
             vals[rows_, 3] = np.where(fin_, out_.cpu().numpy(), np.nan)
+        if wout_ is not None:
+            vals[rows_, WSS_COLUMNS["wss"]] = np.where(fin_, wout_.cpu().numpy(), np.nan)
         for first, pair_ in ((NCOL, qout_), (NCOL + 2, dout_), (NCOL + 4, sout_)):
             if pair_ is not None:
                 vals[rows_, first:first + pair_.shape[1]] = np.where(
@@ -450,10 +468,11 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
             qplan = SegSnrPlan(cl) if quality else None
             dplan = LpcPlan(cl) if distortion else None
             pplan = SiSdrPlan(cl, nz) if separation else None
+            wplan = WssPlan(cl) if wss else None
             state = {}
 
             def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, qplan=qplan,
-                        dplan=dplan, pplan=pplan, state=state):
+                        dplan=dplan, pplan=pplan, wplan=wplan, state=state):
                 """one n_fft's cells are final: queue their scores on the side stream"""
                 idx = np.asarray(p.idx, dtype=np.int64)
                 lg = lag if lag is not None else np.zeros(len(idx), dtype=np.int64)
@@ -464,7 +483,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
                 lag_d = torch.as_tensor(np.asarray(lg, dtype=np.int32)).cuda()
                 y = p.y_all.view(-1)  # the run's waveform buffer (every n_fft's rows)
                 side.wait_stream(main)
-                out = qout = dout = sout = None
+                out = qout = dout = sout = wout = None
                 with torch.cuda.stream(side):
                     if splan is not None:
                         out = splan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
@@ -474,11 +493,13 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
                         dout = dplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     if pplan is not None:
                         sout = pplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
+                    if wplan is not None:
+                        wout = wplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 state["ev"] = ev
-                inflight.append((js[idx], fin, out, qout, dout, sout, ev,
-                                 (y, off_d, sig_d, lag_d, splan, qplan, dplan, pplan)))
+                inflight.append((js[idx], fin, out, qout, dout, sout, wout, ev,
+                                 (y, off_d, sig_d, lag_d, splan, qplan, dplan, pplan, wplan)))
                 while len(inflight) > 2:  # bound the STOI scratch held in flight
                     collect(inflight.pop(0))
 
@@ -525,7 +546,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
 def gather_records(local, n_total, group=None, device=None):
     """All-gather per-cell records [n_local, 1 + NCOL] (RECORD_FIELDS; 1 + NCOL + 2
     with the quality columns, + 4 with the distortion columns, + 7 with the
-    separation columns) from every rank into one [n_total, width - 1]
+    separation columns, + 8 with the wss column) from every rank into one [n_total, width - 1]
     table indexed by cell_id.  The width is the records' own (every rank's
     alike).  Fixed-size rows padded to the largest shard so one
     all_gather_into_tensor moves them."""
@@ -635,9 +656,11 @@ def select_best(specs, table, objective="snr", tol=None):
     "sisdr" / "sisir" / "sisar" (a separation=True table) are maximised from
     -inf like the dB objectives above; a value that is not finite is skipped the
     way a NaN is (+inf: a test signal that is the clean one scaled, or no
-    interference left, which the tolerance scan could not rank)."""
+    interference left, which the tolerance scan could not rank).
+
+    "wss" (a wss=True table) is minimised like "llr"."""
     best = _select_best(specs, table, objective, tol)
-    if objective in DISTORTION_COLUMNS:  # -(-v) is v, bit for bit
+    if objective in DISTORTION_COLUMNS or objective in WSS_COLUMNS:  # -(-v) is v, bit for bit
         best = OrderedDict((k, (win, None if sc is None else -sc)) for k, (win, sc) in best.items())
     return best
 
@@ -660,6 +683,11 @@ def _select_best(specs, table, objective, tol):
         if np.ndim(table) != 2 or np.shape(table)[1] <= col:
             raise ValueError(f"objective {objective!r} needs a separation=True table of "
                              f"{NCOL + 7} columns, this one has {np.shape(table)[-1]}")
+    elif objective in WSS_COLUMNS:
+        col, sign = WSS_COLUMNS[objective], -1.0
+        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
+            raise ValueError(f"objective {objective!r} needs a wss=True table of "
+                             f"{NCOL + 8} columns, this one has {np.shape(table)[-1]}")
     elif objective in ("snr", "stoi"):
         col = TABLE_COLUMN[objective]
     else:
@@ -709,7 +737,7 @@ def _select_best(specs, table, objective, tol):
 
 
 def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
-             extended=False, quality=False, distortion=False, separation=False):
+             extended=False, quality=False, distortion=False, separation=False, wss=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
@@ -722,7 +750,9 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     distortion=True: NCOL + 4 columns (the quality columns, NaN without
     quality=True, then DISTORTION_COLUMNS: llr, cep), likewise.
     separation=True: NCOL + 7 columns (the quality and distortion columns, NaN
-    unless asked for, then SEPARATION_COLUMNS: sisdr, sisir, sisar), likewise."""
+    unless asked for, then SEPARATION_COLUMNS: sisdr, sisir, sisar), likewise.
+    wss=True: NCOL + 8 columns (all of those, NaN unless asked for, then
+    WSS_COLUMNS: wss), likewise."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
@@ -730,19 +760,20 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     lengths = [len(x) for x in noisy]
     rank_of, _ = assign_shards(specs, lengths, world)
     ids = np.nonzero(rank_of == rank)[0]
-    ncol = table_width(quality, distortion, separation)
-    if compute is None and (extended or quality or distortion or separation):
+    ncol = table_width(quality, distortion, separation, wss)
+    if compute is None and (extended or quality or distortion or separation or wss):
         def compute(clean, noisy, specs, ids):
             return engine_compute(clean, noisy, specs, ids,
                                   stoi="extended" if extended else True, quality=quality,
-                                  distortion=distortion, separation=separation)
+                                  distortion=distortion, separation=separation, wss=wss)
     compute = compute or engine_compute
     vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, ncol))
     if np.ndim(vals) != 2 or np.shape(vals)[1] != ncol:
         raise ValueError(f"compute returned rows of shape {np.shape(vals)}, expected "
                          f"{ncol} columns (quality={bool(quality)}"
                          + (", distortion=True" if distortion else "")
-                         + (", separation=True)" if separation else ")"))
+                         + (", separation=True" if separation else "")
+                         + (", wss=True)" if wss else ")"))
     if not dist_on and len(ids) == len(specs):  # one process, every cell in order: no gather
         table = np.asarray(vals, dtype=np.float64)
     else:
@@ -1001,7 +1032,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
               group=None, device=None, extended=False, quality=False, distortion=False,
-              separation=False):
+              separation=False, wss=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
@@ -1027,17 +1058,21 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     written as ..._optimized_sisdr.wav and each row gains sisdr_noisy,
     sisdr_best, that cell's sisir_sisdropt and sisar_sisdropt (how its error
     splits), best_params_sisdr and snr_sisdropt (means in summary_means.json).
-    The SI-SIR and SI-SAR winners are select_best's."""
+    The SI-SIR and SI-SAR winners are select_best's.
+    wss=True: the cells are also scored by the weighted spectral slope distance;
+    the WSS-best (lowest) cell's waveform is written as ..._optimized_wss.wav and
+    each row gains wss_noisy, wss_best, best_params_wss and snr_wssopt (means in
+    summary_means.json)."""
     import torch
     import torch.distributed as dist
     from . import results
     from .engine import Engine
-    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan
+    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan, WssPlan
     grids = grids or ALGORITHM_GRIDS
     algorithms = list(algorithms or grids)
     specs = job_specs(len(noisy), algorithms, grids)
     table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
-                           quality=quality, distortion=distortion, separation=separation)
+                           quality=quality, distortion=distortion, separation=separation, wss=wss)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
@@ -1045,6 +1080,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     best_fw = select_best(specs, table, "fwsegsnr") if quality else None
     best_llr = select_best(specs, table, "llr") if distortion else None
     best_sdr = select_best(specs, table, "sisdr") if separation else None
+    best_wss = select_best(specs, table, "wss") if wss else None
     eng = Engine()
     rows = []
     for pair, stem in enumerate(stems):
@@ -1067,6 +1103,10 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         if separation:
             pplan = SiSdrPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
             p_noisy = _finite(pplan.score(nf, [0], [0], clip=False)[0, 0])
+        w_noisy = None
+        if wss:
+            wplan = WssPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
+            w_noisy = _opt(wplan.score(nf, [0], [0], clip=False)[0])
         x = torch.as_tensor(n).cuda().view(1, -1)
         cl = torch.as_tensor(c).cuda().view(1, -1)
         for alg in algorithms:
@@ -1079,8 +1119,9 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
             fid, fscore = best_fw[(pair, alg)] if quality else (-1, None)
             lid, lscore = best_llr[(pair, alg)] if distortion else (-1, None)
             pid, pscore = best_sdr[(pair, alg)] if separation else (-1, None)
+            wid, wscore = best_wss[(pair, alg)] if wss else (-1, None)
             for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid), ("llr", lid),
-                           ("sisdr", pid)):
+                           ("sisdr", pid), ("wss", wid)):
                 if k < 0:
                     continue
                 res = eng.run(x, [(0, alg, specs[k][2])], clean=cl, want_waveforms=True, align=True)
@@ -1109,7 +1150,12 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                     sisir_sisdropt=None if pid < 0 else _finite(table[pid, NCOL + 5]),
                     sisar_sisdropt=None if pid < 0 else _finite(table[pid, NCOL + 6]),
                     sisdr_params=None if pid < 0 else specs[pid][2],
-                    snr_sisdropt=None if pid < 0 else float(table[pid, 1])))))
+                    snr_sisdropt=None if pid < 0 else float(table[pid, 1]))),
+                **({} if not wss else dict(
+                    wss_noisy=w_noisy,
+                    wss_best=None if wid < 0 else float(wscore),
+                    wss_params=None if wid < 0 else specs[wid][2],
+                    snr_wssopt=None if wid < 0 else float(table[wid, 1])))))
             if extended:
                 rows[-1]["stoi_extended"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
