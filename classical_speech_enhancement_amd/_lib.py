@@ -3,6 +3,10 @@ include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
 include/cse_wss.h, include/cse_sisdr.h and include/cse_logerr.h).
 
+Entry points that share a signature are declared in one loop: the noise
+trackers (TRACKER_EXPORTS) and the waveform scores on the segSNR interface
+(CELL_SCORES / CELL_SCORE_EXPORTS).
+
 The product path has no CPU fallback: if the shared library (built for gfx950
 by ``__graft_entry__.build()``) is missing, every entry point raises.
 """
@@ -120,21 +124,21 @@ EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_stoi_cells_sr")
 # include/cse_estoi.h (extended STOI), a header of its own: EXPORTS is what cse.h declares
 EXPORTS_ESTOI = ("cse_estoi_workspace_bytes", "cse_estoi_prepare", "cse_estoi_cells")
-# include/cse_segsnr.h (segmental and frequency-weighted segmental SNR), likewise
-EXPORTS_SEGSNR = ("cse_segsnr_workspace_bytes", "cse_segsnr_prepare", "cse_segsnr_scratch_bytes",
-                  "cse_segsnr_cells")
+# the waveform scores that share one interface, each with a header of its own,
+# include/cse_<name>.h: segsnr (segmental and frequency-weighted segmental SNR),
+# lpc (log-likelihood ratio and LPC cepstrum distance) and wss (weighted spectral
+# slope distance); name -> output pointers of cse_<name>_cells
+CELL_SCORES = {"segsnr": 2, "lpc": 2, "wss": 1}
+CELL_SCORE_EXPORTS = {s: tuple(f"cse_{s}_{e}" for e in ("workspace_bytes", "prepare",
+                                                       "scratch_bytes", "cells"))
+                      for s in CELL_SCORES}
+EXPORTS_SEGSNR, EXPORTS_LPC, EXPORTS_WSS = CELL_SCORE_EXPORTS.values()
 # the noise trackers (NOISE's methods after the reference's three), each with a
 # header of its own, include/cse_<name>.h: name -> (default-parameters entry,
 # estimate entry); the four names are what the per-tracker tests read
 TRACKER_EXPORTS = {t: (f"cse_{t}_default_params", f"cse_noise_{t}")
                    for t, code in NOISE.items() if code > 2}
 EXPORTS_MCRA, EXPORTS_SPP, EXPORTS_MINSTAT, EXPORTS_IMCRA = TRACKER_EXPORTS.values()
-# include/cse_lpc.h (log-likelihood ratio and LPC cepstrum distance), likewise
-EXPORTS_LPC = ("cse_lpc_workspace_bytes", "cse_lpc_prepare", "cse_lpc_scratch_bytes",
-               "cse_lpc_cells")
-# include/cse_wss.h (weighted spectral slope distance), likewise
-EXPORTS_WSS = ("cse_wss_workspace_bytes", "cse_wss_prepare", "cse_wss_scratch_bytes",
-               "cse_wss_cells")
 # include/cse_sisdr.h (SI-SDR, SI-SIR and SI-SAR), likewise
 EXPORTS_SISDR = ("cse_sisdr_workspace_bytes", "cse_sisdr_prepare", "cse_sisdr_scratch_bytes",
                  "cse_sisdr_cells")
@@ -235,30 +239,15 @@ def load(path=LIB_PATH):
         getattr(lib, default_entry).argtypes = [P]
         getattr(lib, entry).restype = i32
         getattr(lib, entry).argtypes = [P, i64, i32, i32, P, f64, P, P]
-    lib.cse_segsnr_workspace_bytes.restype = i64
-    lib.cse_segsnr_workspace_bytes.argtypes = [i64, i64, i32]
-    lib.cse_segsnr_prepare.restype = i32
-    lib.cse_segsnr_prepare.argtypes = [P, i64, i64, i32, P, P]
-    lib.cse_segsnr_scratch_bytes.restype = i64
-    lib.cse_segsnr_scratch_bytes.argtypes = [i64, i64, i32]
-    lib.cse_segsnr_cells.restype = i32
-    lib.cse_segsnr_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P, P]
-    lib.cse_lpc_workspace_bytes.restype = i64
-    lib.cse_lpc_workspace_bytes.argtypes = [i64, i64, i32]
-    lib.cse_lpc_prepare.restype = i32
-    lib.cse_lpc_prepare.argtypes = [P, i64, i64, i32, P, P]
-    lib.cse_lpc_scratch_bytes.restype = i64
-    lib.cse_lpc_scratch_bytes.argtypes = [i64, i64, i32]
-    lib.cse_lpc_cells.restype = i32
-    lib.cse_lpc_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P, P]
-    lib.cse_wss_workspace_bytes.restype = i64
-    lib.cse_wss_workspace_bytes.argtypes = [i64, i64, i32]
-    lib.cse_wss_prepare.restype = i32
-    lib.cse_wss_prepare.argtypes = [P, i64, i64, i32, P, P]
-    lib.cse_wss_scratch_bytes.restype = i64
-    lib.cse_wss_scratch_bytes.argtypes = [i64, i64, i32]
-    lib.cse_wss_cells.restype = i32
-    lib.cse_wss_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
+    for score, n_out in CELL_SCORES.items():
+        size, prepare, scratch, cells = (getattr(lib, e) for e in CELL_SCORE_EXPORTS[score])
+        size.restype = scratch.restype = i64
+        size.argtypes = [i64, i64, i32]
+        scratch.argtypes = [i64, i64, i32]
+        prepare.restype = cells.restype = i32
+        prepare.argtypes = [P, i64, i64, i32, P, P]
+        # the test signals and their indices, the plan, scratch, the outputs, the stream
+        cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P] + [P] * n_out + [P]
     lib.cse_sisdr_workspace_bytes.restype = i64
     lib.cse_sisdr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_sisdr_prepare.restype = i32

@@ -52,6 +52,13 @@ NoiseErrPlan scores noise-PSD estimates, not waveforms: the logarithmic
 estimation error of include/cse_logerr.h against the smoothed power of
 noisy - clean (cse_logerr_reference / cse_logerr_rows), split into over- and
 under-estimation, per row and on request per frame.
+
+What the waveform plans share is written once: _cell_index checks every
+score_async's y and index arrays, SegSnrPlan._launch is the chunked launch of
+the three plans on the segSNR interface, and _pair_score is the scalar wrapper
+(two equal-length signals, one plan, one score, NaN raises) behind stoi, segsnr,
+fwsegsnr, llr, cepstrum_distance and wss.  evaluate_audio_quality's optional
+groups follow scores.FAMILIES and find calculate_<name> by name.
 """
 
 import ctypes
@@ -62,6 +69,7 @@ import torch
 
 from . import _lib
 from .engine import _ptr, _stream
+from .scores import requested
 
 STOI_SR = 16000
 # cells per cse_stoi_cells launch: bounds the envelope scratch (Mmax x 64 B per cell)
@@ -76,6 +84,53 @@ def _gpu_visible():
     if _GPU is None:
         _GPU = bool(torch.cuda.is_available())
     return _GPU
+
+
+def _cell_index(plan, y, y_offset, sig_of, lag):
+    """Every plan's checks of score_async's y and index arrays: (y_offset,
+    sig_of, lag or None) on the plan's device, and the number of cells.  Host
+    arrays are validated against the plan's S and L and uploaded on the current
+    stream; cuda tensors get every check that needs no host synchronisation
+    (the value ranges are the caller's; the kernels read int64 / int32 / int32)."""
+    dev = plan.clean.device
+    if y.dtype != torch.float32 or not y.is_cuda:
+        raise ValueError("y must be a float32 cuda tensor")
+    if torch.is_tensor(y_offset):
+        off, sig = y_offset, sig_of
+        if not torch.is_tensor(sig):
+            raise ValueError("sig_of must be a cuda tensor when y_offset is one")
+        if off.dtype != torch.int64 or sig.dtype != torch.int32:
+            raise ValueError("device y_offset / sig_of must be int64 / int32")
+        if off.device != dev or sig.device != dev:
+            raise ValueError("device y_offset / sig_of must live on the clean signal's GPU")
+        if not (off.is_contiguous() and sig.is_contiguous()):
+            raise ValueError("device y_offset / sig_of must be contiguous")
+        n = int(off.numel())
+        if int(sig.numel()) != n:
+            raise ValueError("y_offset and sig_of differ in length")
+    else:
+        off_h = np.asarray(y_offset, dtype=np.int64)
+        sig_h = np.asarray(sig_of, dtype=np.int32)
+        n = len(off_h)
+        if len(sig_h) != n:
+            raise ValueError("y_offset and sig_of differ in length")
+        if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= plan.S):
+            raise ValueError("sig_of out of range")
+        if n and (int(off_h.min()) < 0 or int(off_h.max()) + plan.L > y.numel()):
+            raise ValueError("a cell's output runs past the end of y")
+        off = torch.as_tensor(off_h, device=dev)
+        sig = torch.as_tensor(sig_h, device=dev)
+    lg = None
+    if lag is not None:
+        if torch.is_tensor(lag):
+            if lag.device != dev:
+                raise ValueError("device lag must live on the clean signal's GPU")
+            lg = lag.to(torch.int32).contiguous()
+        else:
+            lg = torch.as_tensor(np.asarray(lag, dtype=np.int32), device=dev)
+        if int(lg.numel()) != n:
+            raise ValueError("lag and y_offset differ in length")
+    return off, sig, lg, n
 
 
 class StoiPlan:
@@ -121,50 +176,16 @@ class StoiPlan:
         given as cuda tensors (int64 / int32 / int32) they are taken as they
         are, with no host synchronisation (the caller validated them)."""
         dev = self.clean.device
-        if y.dtype != torch.float32 or not y.is_cuda:
-            raise ValueError("y must be a float32 cuda tensor")
-        if torch.is_tensor(y_offset):
-            # device indices: every check that needs no host synchronisation
-            # (the value ranges are the caller's; the kernel reads int64 / int32)
-            off, sig = y_offset, sig_of
-            if not torch.is_tensor(sig):
-                raise ValueError("sig_of must be a cuda tensor when y_offset is one")
-            if off.dtype != torch.int64 or sig.dtype != torch.int32:
-                raise ValueError("device y_offset / sig_of must be int64 / int32")
-            if off.device != dev or sig.device != dev:
-                raise ValueError("device y_offset / sig_of must live on the clean signal's GPU")
-            if not (off.is_contiguous() and sig.is_contiguous()):
-                raise ValueError("device y_offset / sig_of must be contiguous")
-            n = int(off.numel())
-            if int(sig.numel()) != n:
-                raise ValueError("y_offset and sig_of differ in length")
-            if torch.is_tensor(lag) and (lag.dtype != torch.int32 or lag.device != dev
-                                         or not lag.is_contiguous() or int(lag.numel()) != n):
+        if torch.is_tensor(lag):
+            # this plan alone takes a device lag as it is, like the device
+            # indices, and with host indices moves a lag tensor to its GPU
+            if not torch.is_tensor(y_offset):
+                lag = lag.to(dev)
+            elif lag.dtype != torch.int32 or lag.device != dev or not lag.is_contiguous() \
+                    or lag.numel() != y_offset.numel():
                 raise ValueError("device lag must be a contiguous int32 tensor of n entries "
                                  "on the clean signal's GPU")
-        else:
-            off_h = np.asarray(y_offset, dtype=np.int64)
-            sig_h = np.asarray(sig_of, dtype=np.int32)
-            n = len(off_h)
-            if len(sig_h) != n:
-                raise ValueError("y_offset and sig_of differ in length")
-            if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= self.S):
-                raise ValueError("sig_of out of range")
-            if n and (int(off_h.min()) < 0 or int(off_h.max()) + self.L > y.numel()):
-                raise ValueError("a cell's output runs past the end of y")
-            off = torch.as_tensor(off_h, device=dev)
-            sig = torch.as_tensor(sig_h, device=dev)
-        lg = None
-        if lag is not None:
-            if torch.is_tensor(lag):
-                lg = lag.to(dev, torch.int32).contiguous()
-            else:
-                lag_h = np.asarray(lag, dtype=np.int32)
-                if len(lag_h) != n:
-                    raise ValueError("lag and y_offset differ in length")
-                lg = torch.as_tensor(lag_h, device=dev)
-            if int(lg.numel()) != n:
-                raise ValueError("lag and y_offset differ in length")
+        off, sig, lg, n = _cell_index(self, y, y_offset, sig_of, lag)
         if out is None:
             out = torch.empty(n, dtype=torch.float64, device=dev)
         for s in range(0, n, STOI_CHUNK):
@@ -254,13 +275,22 @@ class SegSnrPlan:
         first, second = self._WHICH
         if which not in ("both", first, second):
             raise ValueError(f"which={which!r}: 'both', {first!r} or {second!r}")
-        off, sig, lg, n = self._cell_index(y, y_offset, sig_of, lag)
+        off, sig, lg, n = _cell_index(self, y, y_offset, sig_of, lag)
         if out is None:
             out = torch.empty((n, 2), dtype=torch.float64, device=dev)
         if out.shape != (n, 2) or out.dtype != torch.float64 or not out.is_contiguous():
             raise ValueError("out must be a contiguous [n, 2] float64 tensor")
         # the library writes one column each: planar scratch rows, then one copy
         cols = torch.full((2, n), float("nan"), dtype=torch.float64, device=dev)
+        self._launch(y, off, sig, lg, n, clip, (None if which == second else cols[0],
+                                                None if which == first else cols[1]))
+        out.copy_(cols.t())
+        return out
+
+    def _launch(self, y, off, sig, lg, n, clip, outs):
+        """The cells kernel over n cells, cells_per_launch() at a time; outs: one
+        [n] f64 row per output pointer of the entry point, None for a score that
+        is not asked for."""
         step = self.cells_per_launch()
         for s in range(0, n, step):
             m = min(step, n - s)
@@ -269,53 +299,8 @@ class SegSnrPlan:
                 _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
                 self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
                 None if scratch is None else _ptr(scratch),
-                None if which == second else _ptr(cols[0, s:]),
-                None if which == first else _ptr(cols[1, s:]), _stream()), f"{self._PREFIX}_cells")
-        out.copy_(cols.t())
-        return out
-
-    def _cell_index(self, y, y_offset, sig_of, lag):
-        """score_async's checks of y and the index arrays: (y_offset, sig_of, lag
-        or None) on the device, and the number of cells."""
-        dev = self.clean.device
-        if y.dtype != torch.float32 or not y.is_cuda:
-            raise ValueError("y must be a float32 cuda tensor")
-        if torch.is_tensor(y_offset):
-            off, sig = y_offset, sig_of
-            if not torch.is_tensor(sig):
-                raise ValueError("sig_of must be a cuda tensor when y_offset is one")
-            if off.dtype != torch.int64 or sig.dtype != torch.int32:
-                raise ValueError("device y_offset / sig_of must be int64 / int32")
-            if off.device != dev or sig.device != dev:
-                raise ValueError("device y_offset / sig_of must live on the clean signal's GPU")
-            if not (off.is_contiguous() and sig.is_contiguous()):
-                raise ValueError("device y_offset / sig_of must be contiguous")
-            n = int(off.numel())
-            if int(sig.numel()) != n:
-                raise ValueError("y_offset and sig_of differ in length")
-        else:
-            off_h = np.asarray(y_offset, dtype=np.int64)
-            sig_h = np.asarray(sig_of, dtype=np.int32)
-            n = len(off_h)
-            if len(sig_h) != n:
-                raise ValueError("y_offset and sig_of differ in length")
-            if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= self.S):
-                raise ValueError("sig_of out of range")
-            if n and (int(off_h.min()) < 0 or int(off_h.max()) + self.L > y.numel()):
-                raise ValueError("a cell's output runs past the end of y")
-            off = torch.as_tensor(off_h, device=dev)
-            sig = torch.as_tensor(sig_h, device=dev)
-        lg = None
-        if lag is not None:
-            if torch.is_tensor(lag):
-                if lag.device != dev:
-                    raise ValueError("device lag must live on the clean signal's GPU")
-                lg = lag.to(torch.int32).contiguous()
-            else:
-                lg = torch.as_tensor(np.asarray(lag, dtype=np.int32), device=dev)
-            if int(lg.numel()) != n:
-                raise ValueError("lag and y_offset differ in length")
-        return off, sig, lg, n
+                *(None if o is None else _ptr(o[s:]) for o in outs), _stream()),
+                f"{self._PREFIX}_cells")
 
     def score(self, y, y_offset, sig_of, lag=None, clip=True, which="both"):
         """score_async, synchronised: [n, 2] numpy (segsnr, fwsegsnr); NaN: no
@@ -350,20 +335,12 @@ class WssPlan(SegSnrPlan):
     def score_async(self, y, y_offset, sig_of, lag=None, clip=True, out=None):
         """Enqueue the score of every cell; returns the [n] f64 cuda result.  The
         arguments are SegSnrPlan.score_async's."""
-        off, sig, lg, n = self._cell_index(y, y_offset, sig_of, lag)
+        off, sig, lg, n = _cell_index(self, y, y_offset, sig_of, lag)
         if out is None:
             out = torch.empty(n, dtype=torch.float64, device=self.clean.device)
         if out.shape != (n,) or out.dtype != torch.float64 or not out.is_contiguous():
             raise ValueError("out must be a contiguous [n] float64 tensor")
-        step = self.cells_per_launch()
-        for s in range(0, n, step):
-            m = min(step, n - s)
-            scratch = self._scratch_for(m)
-            _lib.check(self._fn("cells")(
-                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
-                self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
-                None if scratch is None else _ptr(scratch), _ptr(out[s:]), _stream()),
-                f"{self._PREFIX}_cells")
+        self._launch(y, off, sig, lg, n, clip, (out,))
         return out
 
     def score(self, y, y_offset, sig_of, lag=None, clip=True):
@@ -415,43 +392,7 @@ class SiSdrPlan:
         dev = self.clean.device
         if which not in ("all", "sisdr"):
             raise ValueError(f"which={which!r}: 'all' or 'sisdr'")
-        if y.dtype != torch.float32 or not y.is_cuda:
-            raise ValueError("y must be a float32 cuda tensor")
-        if torch.is_tensor(y_offset):
-            off, sig = y_offset, sig_of
-            if not torch.is_tensor(sig):
-                raise ValueError("sig_of must be a cuda tensor when y_offset is one")
-            if off.dtype != torch.int64 or sig.dtype != torch.int32:
-                raise ValueError("device y_offset / sig_of must be int64 / int32")
-            if off.device != dev or sig.device != dev:
-                raise ValueError("device y_offset / sig_of must live on the clean signal's GPU")
-            if not (off.is_contiguous() and sig.is_contiguous()):
-                raise ValueError("device y_offset / sig_of must be contiguous")
-            n = int(off.numel())
-            if int(sig.numel()) != n:
-                raise ValueError("y_offset and sig_of differ in length")
-        else:
-            off_h = np.asarray(y_offset, dtype=np.int64)
-            sig_h = np.asarray(sig_of, dtype=np.int32)
-            n = len(off_h)
-            if len(sig_h) != n:
-                raise ValueError("y_offset and sig_of differ in length")
-            if n and (int(sig_h.min()) < 0 or int(sig_h.max()) >= self.S):
-                raise ValueError("sig_of out of range")
-            if n and (int(off_h.min()) < 0 or int(off_h.max()) + self.L > y.numel()):
-                raise ValueError("a cell's output runs past the end of y")
-            off = torch.as_tensor(off_h, device=dev)
-            sig = torch.as_tensor(sig_h, device=dev)
-        lg = None
-        if lag is not None:
-            if torch.is_tensor(lag):
-                if lag.device != dev:
-                    raise ValueError("device lag must live on the clean signal's GPU")
-                lg = lag.to(torch.int32).contiguous()
-            else:
-                lg = torch.as_tensor(np.asarray(lag, dtype=np.int32), device=dev)
-            if int(lg.numel()) != n:
-                raise ValueError("lag and y_offset differ in length")
+        off, sig, lg, n = _cell_index(self, y, y_offset, sig_of, lag)
         if out is None:
             out = torch.empty((n, 3), dtype=torch.float64, device=dev)
         if out.shape != (n, 3) or out.dtype != torch.float64 or not out.is_contiguous():
@@ -475,16 +416,37 @@ class SiSdrPlan:
         return self.score_async(y, y_offset, sig_of, lag, clip, which=which).cpu().numpy()
 
 
-def si_sdr(x, y, noisy=None, zero_mean=True):
-    """SI-SDR in dB (include/cse_sisdr.h) of y against the clean x; with noisy
-    (the unprocessed input, x plus the interference) the triple (si_sdr, si_sir,
-    si_sar).  Values may be +-inf or NaN as the header's IEEE rules give them."""
+def _pair_signals(x, y, what):
+    """Two equal-length non-empty 1-D signals as float64, or the scalars' errors."""
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     if x.shape != y.shape:
         raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
     if x.ndim != 1 or x.size == 0:
-        raise ValueError("si_sdr expects non-empty 1-D signals")
+        raise ValueError(f"{what} expects non-empty 1-D signals")
+    return x, y
+
+
+def _pair_score(cls, x, y, what, which=None, nan_message="no non-silent 30-ms frame", **plan_kw):
+    """One score of y against the clean x through a one-signal plan of ``cls``:
+    its column ``which`` when the plan scores several; a NaN raises."""
+    x, y = _pair_signals(x, y, what)
+    plan = cls(torch.as_tensor(x).cuda().view(1, -1), **plan_kw)
+    yd = torch.as_tensor(y.astype(np.float32)).cuda()
+    if which is None:
+        v = float(plan.score(yd, [0], [0], clip=False)[0])
+    else:
+        v = float(plan.score(yd, [0], [0], clip=False, which=which)[0, cls._WHICH.index(which)])
+    if math.isnan(v):
+        raise ValueError(nan_message)
+    return v
+
+
+def si_sdr(x, y, noisy=None, zero_mean=True):
+    """SI-SDR in dB (include/cse_sisdr.h) of y against the clean x; with noisy
+    (the unprocessed input, x plus the interference) the triple (si_sdr, si_sir,
+    si_sar).  Values may be +-inf or NaN as the header's IEEE rules give them."""
+    x, y = _pair_signals(x, y, "si_sdr")
     nz = None
     if noisy is not None:
         nz = np.asarray(noisy, dtype=np.float64)
@@ -634,49 +596,20 @@ def noise_logerr(clean, noisy, N, n_fft, hop_length, per_frame=False, **kw):
     return out
 
 
-def _plan_pair(cls, x, y, fs, which):
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    if x.shape != y.shape:
-        raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
-    if x.ndim != 1 or x.size == 0:
-        raise ValueError(f"{which} expects non-empty 1-D signals")
-    plan = cls(torch.as_tensor(x).cuda().view(1, -1), fs)
-    yd = torch.as_tensor(y.astype(np.float32)).cuda()
-    v = float(plan.score(yd, [0], [0], clip=False, which=which)[0, cls._WHICH.index(which)])
-    if math.isnan(v):
-        raise ValueError("no non-silent 30-ms frame")
-    return v
-
-
-def _segsnr_pair(x, y, fs, which):
-    return _plan_pair(SegSnrPlan, x, y, fs, which)
-
-
 def llr(x, y, fs):
     """Log-likelihood ratio (include/cse_lpc.h) of y against the clean x; lower is better."""
-    return _plan_pair(LpcPlan, x, y, fs, "llr")
+    return _pair_score(LpcPlan, x, y, "llr", "llr", sr=fs)
 
 
 def cepstrum_distance(x, y, fs):
     """LPC cepstrum distance (include/cse_lpc.h) of y against the clean x; lower is better."""
-    return _plan_pair(LpcPlan, x, y, fs, "cep")
+    return _pair_score(LpcPlan, x, y, "cep", "cep", sr=fs)
 
 
 def wss(x, y, fs):
     """Weighted spectral slope distance (include/cse_wss.h) of y against the clean
     x; lower is better."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    if x.shape != y.shape:
-        raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
-    if x.ndim != 1 or x.size == 0:
-        raise ValueError("wss expects non-empty 1-D signals")
-    plan = WssPlan(torch.as_tensor(x).cuda().view(1, -1), fs)
-    v = float(plan.score(torch.as_tensor(y.astype(np.float32)).cuda(), [0], [0], clip=False)[0])
-    if math.isnan(v):
-        raise ValueError("no non-silent 30-ms frame")
-    return v
+    return _pair_score(WssPlan, x, y, "wss", sr=fs)
 
 
 def composite(pesq, llr, wss, segsnr):
@@ -704,12 +637,12 @@ def composite(pesq, llr, wss, segsnr):
 
 def segsnr(x, y, fs):
     """Segmental SNR in dB (include/cse_segsnr.h) of y against the clean x."""
-    return _segsnr_pair(x, y, fs, "segsnr")
+    return _pair_score(SegSnrPlan, x, y, "segsnr", "segsnr", sr=fs)
 
 
 def fwsegsnr(x, y, fs):
     """Frequency-weighted segmental SNR in dB (include/cse_segsnr.h)."""
-    return _segsnr_pair(x, y, fs, "fwsegsnr")
+    return _pair_score(SegSnrPlan, x, y, "fwsegsnr", "fwsegsnr", sr=fs)
 
 
 def _calculate_quality(fn, name, clean_reference, test_audio, sr):
@@ -751,18 +684,8 @@ def calculate_wss(clean_reference, test_audio, sr):
 def stoi(x, y, fs_sig, extended=False):
     """pystoi ``stoi(x, y, fs_sig, extended=False)`` on the device; with
     extended=True, extended STOI as include/cse_estoi.h defines it."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    if x.shape != y.shape:
-        raise Exception(f"x and y should have the same length, found {x.shape} and {y.shape}")
-    if x.ndim != 1 or x.size == 0:
-        raise ValueError("stoi expects non-empty 1-D signals")
-    plan = StoiPlan(torch.as_tensor(x).cuda().view(1, -1), fs_sig, extended=extended)
-    yd = torch.as_tensor(y.astype(np.float32)).cuda()
-    v = float(plan.score(yd, [0], [0], clip=False)[0])
-    if math.isnan(v):
-        raise ValueError("no 256-sample frame at 10 kHz")  # pystoi: empty frame array
-    return v
+    return _pair_score(StoiPlan, x, y, "stoi", sr=fs_sig, extended=extended,
+                       nan_message="no 256-sample frame at 10 kHz")  # pystoi: empty frame array
 
 
 def calculate_stoi(clean_reference, test_audio, sr, extended=False):
@@ -856,31 +779,18 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     snr_val = calculate_snr(clean_reference, enhanced_audio)
     if snr_val is not None:
         results["snr_enhanced"] = snr_val
-    if quality:
-        for key, fn in (("segsnr", calculate_segsnr), ("fwsegsnr", calculate_fwsegsnr)):
-            q_noisy = fn(clean_reference, noisy_audio, sr)
-            q_enh = fn(clean_reference, enhanced_audio, sr)
-            if q_noisy is not None and q_enh is not None:
-                results[f"{key}_noisy"] = q_noisy
-                results[f"{key}_enhanced"] = q_enh
-                results[f"{key}_improvement"] = q_enh - q_noisy
-    if distortion:
-        for key, fn in (("llr", calculate_llr), ("cep", calculate_cep)):
-            d_noisy = fn(clean_reference, noisy_audio, sr)
-            d_enh = fn(clean_reference, enhanced_audio, sr)
-            if d_noisy is not None and d_enh is not None:
-                results[f"{key}_noisy"] = d_noisy
-                results[f"{key}_enhanced"] = d_enh
-                results[f"{key}_improvement"] = d_noisy - d_enh
-    if separation:
-        results.update(_separation(clean_reference, noisy_audio, enhanced_audio))
-    if wss:
-        w_noisy = calculate_wss(clean_reference, noisy_audio, sr)
-        w_enh = calculate_wss(clean_reference, enhanced_audio, sr)
-        if w_noisy is not None and w_enh is not None:
-            results["wss_noisy"] = w_noisy
-            results["wss_enhanced"] = w_enh
-            results["wss_improvement"] = w_noisy - w_enh
+    for f in requested(quality=quality, distortion=distortion, separation=separation, wss=wss):
+        if f.plan_takes_noisy:  # scored against the noisy input's interference
+            results.update(_separation(clean_reference, noisy_audio, enhanced_audio))
+            continue
+        for key in f.names:
+            fn = globals()["calculate_" + key]
+            v_noisy = fn(clean_reference, noisy_audio, sr)
+            v_enh = fn(clean_reference, enhanced_audio, sr)
+            if v_noisy is not None and v_enh is not None:
+                results[f"{key}_noisy"] = v_noisy
+                results[f"{key}_enhanced"] = v_enh
+                results[f"{key}_improvement"] = v_enh - v_noisy if f.sign > 0 else v_noisy - v_enh
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:

@@ -32,7 +32,9 @@ cell's sisdr_best, sisir_sisdropt, sisar_sisdropt (the interference and artifact
 parts of its error), best_params_sisdr and snr_sisdropt.  There is no
 sisar_noisy: the unprocessed input's SI-SAR carries no meaning
 (include/cse_sisdr.h).  A wss=True sweep does the same with wss_noisy and the
-WSS-optimal (lowest) cell's wss_best, best_params_wss and snr_wssopt.
+WSS-optimal (lowest) cell's wss_best, best_params_wss and snr_wssopt.  The four
+groups are the records of scores.FAMILIES (row_args, lead, tag); result_row and
+summary_means loop over them.
 """
 
 import json
@@ -40,6 +42,8 @@ import os
 import wave
 
 import numpy as np
+
+from .scores import FAMILIES, row_keys, summary_keys
 
 ROW_KEYS = ("alg", "stem", "sr",
             "stoi_noisy", "pesq_noisy", "snr_noisy",
@@ -56,36 +60,13 @@ SUMMARY_KEYS = (("stoi_noisy_mean", "stoi_noisy"), ("pesq_noisy_mean", "pesq_noi
                 ("snr_balopt_mean", "snr_balopt"), ("snr_snropt_mean", "snr_snropt"))
 
 
-QUALITY_ARGS = ("segsnr_noisy", "fwsegsnr_noisy", "fwsegsnr_best", "fwsegsnr_params",
-                "snr_fwsegopt")
-QUALITY_KEYS = ("segsnr_noisy", "fwsegsnr_noisy", "fwsegsnr_best", "best_params_fwsegsnr",
-                "snr_fwsegopt")
-QUALITY_SUMMARY_KEYS = (("segsnr_noisy_mean", "segsnr_noisy"),
-                        ("fwsegsnr_noisy_mean", "fwsegsnr_noisy"),
-                        ("fwsegsnr_best_mean", "fwsegsnr_best"),
-                        ("snr_fwsegopt_mean", "snr_fwsegopt"))
-
-
-DISTORTION_ARGS = ("llr_noisy", "cep_noisy", "llr_best", "llr_params", "snr_llropt")
-DISTORTION_KEYS = ("llr_noisy", "cep_noisy", "llr_best", "best_params_llr", "snr_llropt")
-DISTORTION_SUMMARY_KEYS = (("llr_noisy_mean", "llr_noisy"), ("cep_noisy_mean", "cep_noisy"),
-                           ("llr_best_mean", "llr_best"), ("snr_llropt_mean", "snr_llropt"))
-
-
-SEPARATION_ARGS = ("sisdr_noisy", "sisdr_best", "sisir_sisdropt", "sisar_sisdropt",
-                   "sisdr_params", "snr_sisdropt")
-SEPARATION_KEYS = ("sisdr_noisy", "sisdr_best", "sisir_sisdropt", "sisar_sisdropt",
-                   "best_params_sisdr", "snr_sisdropt")
-SEPARATION_SUMMARY_KEYS = (("sisdr_noisy_mean", "sisdr_noisy"), ("sisdr_best_mean", "sisdr_best"),
-                           ("sisir_sisdropt_mean", "sisir_sisdropt"),
-                           ("sisar_sisdropt_mean", "sisar_sisdropt"),
-                           ("snr_sisdropt_mean", "snr_sisdropt"))
-
-
-WSS_ARGS = ("wss_noisy", "wss_best", "wss_params", "snr_wssopt")
-WSS_KEYS = ("wss_noisy", "wss_best", "best_params_wss", "snr_wssopt")
-WSS_SUMMARY_KEYS = (("wss_noisy_mean", "wss_noisy"), ("wss_best_mean", "wss_best"),
-                    ("snr_wssopt_mean", "snr_wssopt"))
+# the optional score families' keys (scores.FAMILIES), under their first names
+QUALITY_ARGS, DISTORTION_ARGS, SEPARATION_ARGS, WSS_ARGS = (
+    f.row_args for f in FAMILIES.values())
+QUALITY_KEYS, DISTORTION_KEYS, SEPARATION_KEYS, WSS_KEYS = (
+    row_keys(f) for f in FAMILIES.values())
+QUALITY_SUMMARY_KEYS, DISTORTION_SUMMARY_KEYS, SEPARATION_SUMMARY_KEYS, WSS_SUMMARY_KEYS = (
+    summary_keys(f) for f in FAMILIES.values())
 
 
 def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
@@ -95,49 +76,31 @@ def result_row(stem, alg, sr, snr_noisy, best_snr, best_params, stoi_noisy=None,
     stoi_stoiopt / snr_stoiopt / best_params_stoi); PESQ fields are None (no
     pesq extension), and so are the PESQ-opt and balance-opt columns
     (:320-333: the balance objective needs PESQ).  The SNR-optimal cell goes
-    to the extra keys snr_snropt / best_params_snr only.  The quality keywords
-    (all or none: segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best, fwsegsnr_params,
-    snr_fwsegopt) add the QUALITY_KEYS of a quality=True sweep, the distortion
-    keywords (all or none: DISTORTION_ARGS) the DISTORTION_KEYS of a
-    distortion=True one, the separation keywords (all or none: SEPARATION_ARGS)
-    the SEPARATION_KEYS of a separation=True one, the WSS keywords (all or none,
-    and a part of them raises TypeError: WSS_ARGS) the WSS_KEYS of a wss=True
-    one."""
+    to the extra keys snr_snropt / best_params_snr only.  Each score family's
+    keywords (scores.FAMILIES: its row_args, all or none; QUALITY_ARGS =
+    segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best, fwsegsnr_params, snr_fwsegopt,
+    DISTORTION_ARGS, SEPARATION_ARGS, WSS_ARGS) add the family's keys
+    (QUALITY_KEYS, ...) of a sweep with its flag, an absent keyword as None; a
+    part of the WSS keywords raises TypeError."""
     row = {k: None for k in ROW_KEYS}
     row.update(alg=alg, stem=stem, sr=int(sr), snr_noisy=snr_noisy,
                best_params_stoi=dict(stoi_params or {}), best_params_pesq={},
                best_params_balanced={}, snr_snropt=best_snr,
                best_params_snr=dict(best_params or {}),
                stoi_noisy=stoi_noisy, stoi_stoiopt=stoi_best, snr_stoiopt=snr_stoiopt)
-    unknown = (set(quality) - set(QUALITY_ARGS) - set(DISTORTION_ARGS) - set(SEPARATION_ARGS)
-               - set(WSS_ARGS))
+    unknown = set(quality).difference(*(f.row_args for f in FAMILIES.values()))
     if unknown:
         raise TypeError(f"result_row: unexpected keywords {sorted(unknown)}")
-    if set(quality) & set(QUALITY_ARGS):
-        row.update(segsnr_noisy=quality.get("segsnr_noisy"),
-                   fwsegsnr_noisy=quality.get("fwsegsnr_noisy"),
-                   fwsegsnr_best=quality.get("fwsegsnr_best"),
-                   best_params_fwsegsnr=dict(quality.get("fwsegsnr_params") or {}),
-                   snr_fwsegopt=quality.get("snr_fwsegopt"))
-    if set(quality) & set(DISTORTION_ARGS):
-        row.update(llr_noisy=quality.get("llr_noisy"), cep_noisy=quality.get("cep_noisy"),
-                   llr_best=quality.get("llr_best"),
-                   best_params_llr=dict(quality.get("llr_params") or {}),
-                   snr_llropt=quality.get("snr_llropt"))
-    if set(quality) & set(SEPARATION_ARGS):
-        row.update(sisdr_noisy=quality.get("sisdr_noisy"), sisdr_best=quality.get("sisdr_best"),
-                   sisir_sisdropt=quality.get("sisir_sisdropt"),
-                   sisar_sisdropt=quality.get("sisar_sisdropt"),
-                   best_params_sisdr=dict(quality.get("sisdr_params") or {}),
-                   snr_sisdropt=quality.get("snr_sisdropt"))
-    given = set(quality) & set(WSS_ARGS)
-    if given and given != set(WSS_ARGS):  # all or none: a lone key would leave a half-filled row
-        raise TypeError(f"result_row: the WSS keywords go together, missing "
-                        f"{sorted(set(WSS_ARGS) - given)}")
-    if given:
-        row.update(wss_noisy=quality.get("wss_noisy"), wss_best=quality.get("wss_best"),
-                   best_params_wss=dict(quality.get("wss_params") or {}),
-                   snr_wssopt=quality.get("snr_wssopt"))
+    for f in FAMILIES.values():
+        given = set(quality) & set(f.row_args)
+        if f.all_or_none and given and given != set(f.row_args):
+            # all or none: a lone key would leave a half-filled row
+            raise TypeError(f"result_row: the {f.flag.upper()} keywords go together, missing "
+                            f"{sorted(set(f.row_args) - given)}")
+        if given:
+            for arg, key in zip(f.row_args, row_keys(f)):
+                v = quality.get(arg)
+                row[key] = dict(v or {}) if arg.endswith("_params") else v
     return row
 
 
@@ -157,18 +120,10 @@ def summary_means(all_results, algorithms):
         entry = {"count": len(rows)}
         for key, field in SUMMARY_KEYS:
             entry[key] = safe_mean([r.get(field) for r in rows])
-        if any("fwsegsnr_best" in r for r in rows):  # a quality=True sweep
-            for key, field in QUALITY_SUMMARY_KEYS:
-                entry[key] = safe_mean([r.get(field) for r in rows])
-        if any("llr_best" in r for r in rows):  # a distortion=True sweep
-            for key, field in DISTORTION_SUMMARY_KEYS:
-                entry[key] = safe_mean([r.get(field) for r in rows])
-        if any("sisdr_best" in r for r in rows):  # a separation=True sweep
-            for key, field in SEPARATION_SUMMARY_KEYS:
-                entry[key] = safe_mean([r.get(field) for r in rows])
-        if any("wss_best" in r for r in rows):  # a wss=True sweep
-            for key, field in WSS_SUMMARY_KEYS:
-                entry[key] = safe_mean([r.get(field) for r in rows])
+        for f in FAMILIES.values():
+            if any(f"{f.lead}_best" in r for r in rows):  # a sweep with the family's flag
+                for key, field in summary_keys(f):
+                    entry[key] = safe_mean([r.get(field) for r in rows])
         out[alg] = entry
     return out
 

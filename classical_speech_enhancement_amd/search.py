@@ -67,6 +67,13 @@ Loizou's composite measures besides PESQ that the other columns do not hold:
 column NCOL + 7 (WSS_COLUMNS) of a table that then always has NCOL + 8 columns,
 the earlier optional columns NaN unless asked for too.  "wss" is minimised.
 
+These four keywords are the records of scores.FAMILIES, in table order; the
+tables, the selection, the sweep's per-family work and the result rows loop
+over the records, and the per-family constants below (QUALITY_COLUMNS, ...) are
+derived from them.  The public signatures keep one keyword per family and pass
+the requested records, or the dict of flags, down.  STOI is no family: it owns
+column 3 of every table and the extended switch.
+
 score_noise_estimators and sweep_tracker judge noise-PSD estimates themselves,
 with no enhancement algorithm on top: the logarithmic estimation error of
 include/cse_logerr.h (cse_logerr_rows) against the smoothed power of the pair's
@@ -81,23 +88,19 @@ from collections import OrderedDict
 
 import numpy as np
 
+from . import scores
 from .parameter_ranges import ALGORITHM_GRIDS, grid_cells
+from .scores import FAMILIES, OBJECTIVES
 from .trackers import TRACKERS
 
 # per-bin cost weights (measured kernel time per frame, OMLSA ~ 3x SS)
 ALGO_WEIGHT = {"spectralSubtractor": 1.0, "wiener": 1.1, "mmse": 2.0, "omlsa": 3.0}
 # tolerance of the best-so-far update per objective (speech_enhancement_comparison.py:183,194,205)
-# segsnr / fwsegsnr (dB): the reference's step for PESQ, the quality objective they stand in for
-# llr / cep: that PESQ step of 1e-3 on a 5-wide scale carried to a 2-wide and a 10-wide one
+# and the optional families' (scores.FAMILIES)
 TOLERANCE = {"stoi": 1e-6, "pesq": 1e-3, "balance": 1e-5, "snr": 1e-5,
-             "segsnr": 1e-3, "fwsegsnr": 1e-3, "llr": 1e-4, "cep": 1e-3,
-             # sisdr / sisir / sisar (dB): the step of the other dB objectives
-             "sisdr": 1e-3, "sisir": 1e-3, "sisar": 1e-3,
              # logerr (dB, sweep_tracker's objectives): the step of the other dB objectives
              "logerr": 1e-3,
-             # wss: the PESQ step of 1e-3 on a 5-wide scale carried to a scale about 100 wide
-             # (2e-2), rounded down to a power of ten
-             "wss": 1e-2}
+             **{name: tol for f in FAMILIES.values() for name, tol in f.tolerance.items()}}
 
 # one float64 row per cell.  lag: finalize_enhanced's alignment lag (0 when
 # not aligned); xstatus: cse_xcorr_lag's status (engine: XCORR_OK, XCORR_FLAT =
@@ -106,31 +109,30 @@ RECORD_FIELDS = ("cell_id", "sse", "snr", "finite", "stoi", "lag", "xstatus")
 TABLE_COLUMN = {"sse": 0, "snr": 1, "finite": 2, "stoi": 3, "lag": 4,
                 "xstatus": 5}  # table = records without cell_id
 NCOL = len(RECORD_FIELDS) - 1
-# quality=True tables carry two more columns after the NCOL ones
-QUALITY_COLUMNS = {"segsnr": 6, "fwsegsnr": 7}
+assert NCOL == scores.NCOL
+# The optional families' columns follow the NCOL ones in registry order: a
+# table is as wide as its last requested family needs, the earlier families'
+# columns NaN unless asked for too.  quality: NCOL + 2 columns; distortion:
+# NCOL + 4, minimised (select_best scans the negated column); separation: NCOL +
+# 7, unbounded dB values of which select_best skips what is not finite; wss:
+# NCOL + 8, minimised.
+QUALITY_COLUMNS, DISTORTION_COLUMNS, SEPARATION_COLUMNS, WSS_COLUMNS = (
+    scores.columns(f) for f in FAMILIES.values())
 # where select_best's scan starts: the reference's -1 (speech_enhancement_comparison.py:126-141)
-# unless the objective's values go below it (dB scores clamped to [-10, 35])
-SCAN_START = {"segsnr": -math.inf, "fwsegsnr": -math.inf, "llr": -math.inf, "cep": -math.inf,
-              "sisdr": -math.inf, "sisir": -math.inf, "sisar": -math.inf, "wss": -math.inf}
-# distortion=True tables have NCOL + 4 columns: the two quality columns (NaN
-# without quality=True), then these.  Lower is better: select_best scans the
-# negated column
-DISTORTION_COLUMNS = {"llr": 8, "cep": 9}
-# separation=True tables have NCOL + 7 columns: the quality and distortion
-# columns (NaN unless asked for too), then these.  Unbounded dB values that may
-# be +-inf or NaN (include/cse_sisdr.h): select_best skips what is not finite
-SEPARATION_COLUMNS = {"sisdr": NCOL + 4, "sisir": NCOL + 5, "sisar": NCOL + 6}
-# wss=True tables have NCOL + 8 columns: the quality, distortion and separation
-# columns (NaN unless asked for too), then this one.  Lower is better:
-# select_best scans the negated column
-WSS_COLUMNS = {"wss": NCOL + 7}
+# unless the objective's values go below it (the families' dB scores and distances)
+SCAN_START = {name: -math.inf for name in OBJECTIVES}
 
 
 def table_width(quality=False, distortion=False, separation=False, wss=False):
     """Columns of a table: NCOL, + 2 with quality, + 4 with distortion (with or
     without quality), + 7 with separation, + 8 with wss (whatever else is asked
     for)."""
-    return NCOL + (8 if wss else 7 if separation else 4 if distortion else 2 if quality else 0)
+    return _width(scores.requested(quality=quality, distortion=distortion, separation=separation,
+                                   wss=wss))
+
+
+def _width(fams):
+    return scores.width(fams[-1]) if fams else NCOL
 # bound on the cell waveforms held at once for STOI scoring (f32 bytes): 48 GiB
 # of the 288 GB HBM, i.e. 10 full 10-s pairs (7,308 computed cells x 640 KB each)
 # per batch, two batches in flight.  100-pair sweep (late r04, call_r04s.sh in profiles/r04_commands.md):
@@ -381,8 +383,8 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     eng = engine or Engine()
     size0 = eng.plan_cache_size
     try:
-        return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, bool(quality),
-                               bool(distortion), bool(separation), bool(wss))
+        return _engine_compute(eng, clean, noisy, specs, ids, align, stoi, scores.requested(
+            quality=quality, distortion=distortion, separation=separation, wss=wss))
     finally:
         if own:
             eng._plan_cache.clear()
@@ -392,13 +394,13 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
                 eng._plan_cache.popitem(last=False)
 
 
-def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, distortion=False,
-                    separation=False, wss=False):
+def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, fams=()):
+    """engine_compute's work; fams: the requested families' records (scores.requested)."""
     import torch
+    from . import metrics
     from .engine import snr_db, spec_fingerprint, structure_digest
-    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan, WssPlan
     # the cell waveforms are scored on the side stream
-    keep = bool(stoi) or quality or distortion or separation or wss
+    keep = bool(stoi) or bool(fams)
     ids = np.asarray(ids, dtype=np.int64)
     lengths = [len(x) for x in noisy]
     js_specs = isinstance(specs, JobSpecs)
@@ -408,7 +410,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
     else:
         comp, back = ids, np.arange(len(ids))
         pair_of = np.fromiter((specs[c][0] for c in comp), dtype=np.int64, count=len(comp))
-    vals = np.full((len(comp), table_width(quality, distortion, separation, wss)), np.nan)
+    vals = np.full((len(comp), _width(fams)), np.nan)
     by_len = OrderedDict()
     upairs, first = np.unique(pair_of, return_index=True)
     for pair in upairs[np.argsort(first, kind="stable")].tolist():  # first-appearance order
@@ -426,16 +428,13 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
     nbatch = 0
 
     def collect(item):
-        rows_, fin_, out_, qout_, dout_, sout_, wout_, ev_, _refs = item
+        rows_, fin_, outs_, ev_, _refs = item
         ev_.synchronize()
-        if out_ is not None:
-            vals[rows_, 3] = np.where(fin_, out_.cpu().numpy(), np.nan)
-        if wout_ is not None:
-            vals[rows_, WSS_COLUMNS["wss"]] = np.where(fin_, wout_.cpu().numpy(), np.nan)
-        for first, pair_ in ((NCOL, qout_), (NCOL + 2, dout_), (NCOL + 4, sout_)):
-            if pair_ is not None:
-                vals[rows_, first:first + pair_.shape[1]] = np.where(
-                    np.asarray(fin_, dtype=bool)[:, None], pair_.cpu().numpy(), np.nan)
+        fin_ = np.asarray(fin_, dtype=bool)[:, None]
+        for first, out_ in outs_:
+            v = out_.cpu().numpy()
+            v = v[:, None] if v.ndim == 1 else v  # [n]: one column
+            vals[rows_, first:first + v.shape[1]] = np.where(fin_, v, np.nan)
 
     sorted_pairs = len(pair_of) < 2 or bool((pair_of[1:] >= pair_of[:-1]).all())
     for L, pairs_l in by_len.items():
@@ -464,15 +463,16 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
             cl = torch.as_tensor(np.stack([np.asarray(clean[p], np.float64) for p in pairs])).cuda()
             cpow = np.array([float(np.dot(np.asarray(clean[p], np.float64),
                                           np.asarray(clean[p], np.float64))) for p in pairs])
-            splan = StoiPlan(cl, extended=(stoi == "extended")) if stoi else None
-            qplan = SegSnrPlan(cl) if quality else None
-            dplan = LpcPlan(cl) if distortion else None
-            pplan = SiSdrPlan(cl, nz) if separation else None
-            wplan = WssPlan(cl) if wss else None
+            # (first column, plan) in launch order: STOI, which is no family (it
+            # owns column 3), then the requested families in registry order
+            plans = [(TABLE_COLUMN["stoi"],
+                      metrics.StoiPlan(cl, extended=(stoi == "extended")))] if stoi else []
+            for f in fams:
+                cls = getattr(metrics, f.plan)
+                plans.append((f.first, cls(cl, nz) if f.plan_takes_noisy else cls(cl)))
             state = {}
 
-            def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, splan=splan, qplan=qplan,
-                        dplan=dplan, pplan=pplan, wplan=wplan, state=state):
+            def on_plan(p, sse, fin, lag, js=js, sig=sig, L=L, plans=plans, state=state):
                 """one n_fft's cells are final: queue their scores on the side stream"""
                 idx = np.asarray(p.idx, dtype=np.int64)
                 lg = lag if lag is not None else np.zeros(len(idx), dtype=np.int64)
@@ -483,23 +483,14 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, quality=False, d
                 lag_d = torch.as_tensor(np.asarray(lg, dtype=np.int32)).cuda()
                 y = p.y_all.view(-1)  # the run's waveform buffer (every n_fft's rows)
                 side.wait_stream(main)
-                out = qout = dout = sout = wout = None
                 with torch.cuda.stream(side):
-                    if splan is not None:
-                        out = splan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
-                    if qplan is not None:
-                        qout = qplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
-                    if dplan is not None:
-                        dout = dplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
-                    if pplan is not None:
-                        sout = pplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
-                    if wplan is not None:
-                        wout = wplan.score_async(y, off_d, sig_d, lag=lag_d, clip=True)
+                    outs = [(first, plan.score_async(y, off_d, sig_d, lag=lag_d, clip=True))
+                            for first, plan in plans]
                     ev = torch.cuda.Event()
                     ev.record(side)
                 state["ev"] = ev
-                inflight.append((js[idx], fin, out, qout, dout, sout, wout, ev,
-                                 (y, off_d, sig_d, lag_d, splan, qplan, dplan, pplan, wplan)))
+                # the last entry keeps what the queued kernels read alive until collect
+                inflight.append((js[idx], fin, outs, ev, (y, off_d, sig_d, lag_d, plans)))
                 while len(inflight) > 2:  # bound the STOI scratch held in flight
                     collect(inflight.pop(0))
 
@@ -660,7 +651,7 @@ def select_best(specs, table, objective="snr", tol=None):
 
     "wss" (a wss=True table) is minimised like "llr"."""
     best = _select_best(specs, table, objective, tol)
-    if objective in DISTORTION_COLUMNS or objective in WSS_COLUMNS:  # -(-v) is v, bit for bit
+    if objective in OBJECTIVES and OBJECTIVES[objective].sign < 0:  # -(-v) is v, bit for bit
         best = OrderedDict((k, (win, None if sc is None else -sc)) for k, (win, sc) in best.items())
     return best
 
@@ -668,26 +659,12 @@ def select_best(specs, table, objective="snr", tol=None):
 def _select_best(specs, table, objective, tol):
     tol = TOLERANCE[objective] if tol is None else tol
     sign, finite_only = 1.0, False
-    if objective in QUALITY_COLUMNS:
-        col = QUALITY_COLUMNS[objective]
+    if objective in OBJECTIVES:
+        f = OBJECTIVES[objective]
+        col, sign, finite_only = scores.columns(f)[objective], float(f.sign), f.finite_only
         if np.ndim(table) != 2 or np.shape(table)[1] <= col:
-            raise ValueError(f"objective {objective!r} needs a quality=True table of "
-                             f"{NCOL + 2} columns, this one has {np.shape(table)[-1]}")
-    elif objective in DISTORTION_COLUMNS:
-        col, sign = DISTORTION_COLUMNS[objective], -1.0
-        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
-            raise ValueError(f"objective {objective!r} needs a distortion=True table of "
-                             f"{NCOL + 4} columns, this one has {np.shape(table)[-1]}")
-    elif objective in SEPARATION_COLUMNS:
-        col, finite_only = SEPARATION_COLUMNS[objective], True
-        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
-            raise ValueError(f"objective {objective!r} needs a separation=True table of "
-                             f"{NCOL + 7} columns, this one has {np.shape(table)[-1]}")
-    elif objective in WSS_COLUMNS:
-        col, sign = WSS_COLUMNS[objective], -1.0
-        if np.ndim(table) != 2 or np.shape(table)[1] <= col:
-            raise ValueError(f"objective {objective!r} needs a wss=True table of "
-                             f"{NCOL + 8} columns, this one has {np.shape(table)[-1]}")
+            raise ValueError(f"objective {objective!r} needs a {f.flag}=True table of "
+                             f"{scores.width(f)} columns, this one has {np.shape(table)[-1]}")
     elif objective in ("snr", "stoi"):
         col = TABLE_COLUMN[objective]
     else:
@@ -760,20 +737,21 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     lengths = [len(x) for x in noisy]
     rank_of, _ = assign_shards(specs, lengths, world)
     ids = np.nonzero(rank_of == rank)[0]
-    ncol = table_width(quality, distortion, separation, wss)
-    if compute is None and (extended or quality or distortion or separation or wss):
+    flags = dict(quality=quality, distortion=distortion, separation=separation, wss=wss)
+    fams = scores.requested(**flags)
+    ncol = _width(fams)
+    if compute is None and (extended or fams):
         def compute(clean, noisy, specs, ids):
             return engine_compute(clean, noisy, specs, ids,
-                                  stoi="extended" if extended else True, quality=quality,
-                                  distortion=distortion, separation=separation, wss=wss)
+                                  stoi="extended" if extended else True, **flags)
     compute = compute or engine_compute
     vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, ncol))
     if np.ndim(vals) != 2 or np.shape(vals)[1] != ncol:
+        # the first family's flag is always shown, the others when set
+        first = next(iter(FAMILIES))
         raise ValueError(f"compute returned rows of shape {np.shape(vals)}, expected "
-                         f"{ncol} columns (quality={bool(quality)}"
-                         + (", distortion=True" if distortion else "")
-                         + (", separation=True" if separation else "")
-                         + (", wss=True)" if wss else ")"))
+                         f"{ncol} columns ({first}={bool(flags[first])}"
+                         + "".join(f", {f.flag}=True" for f in fams if f.flag != first) + ")")
     if not dist_on and len(ids) == len(specs):  # one process, every cell in order: no gather
         table = np.asarray(vals, dtype=np.float64)
     else:
@@ -903,22 +881,11 @@ def _device_stoi(clean, test, sr, extended=False):
     return calculate_stoi(clean, test, sr, extended=extended)
 
 
-def _device_quality(clean, test, sr):
-    """(segsnr, fwsegsnr) of test against clean on the device, None for a failure."""
-    from .metrics import calculate_fwsegsnr, calculate_segsnr
-    return calculate_segsnr(clean, test, sr), calculate_fwsegsnr(clean, test, sr)
-
-
-def _device_distortion(clean, test, sr):
-    """(llr, cep) of test against clean on the device, None for a failure."""
-    from .metrics import calculate_cep, calculate_llr
-    return calculate_llr(clean, test, sr), calculate_cep(clean, test, sr)
-
-
-def _device_separation(clean, noisy, sr):
-    """SI-SDR of the noisy input against clean on the device, None for a failure."""
-    from .metrics import calculate_sisdr
-    return calculate_sisdr(clean, noisy, sr)
+def _device_scores(names, clean, test, sr):
+    """metrics.calculate_<name> of test against clean for each of ``names``, on
+    the device: a tuple, None for a failure."""
+    from . import metrics
+    return tuple(getattr(metrics, "calculate_" + name)(clean, test, sr) for name in names)
 
 
 def _opt(v):
@@ -965,8 +932,8 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     specs = job_specs(1, [alg], grids)
     clean = [np.asarray(clean_reference, np.float64)]
     noisy = [np.asarray(noisy_audio, np.float64)]
-    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended,
-                           quality=quality, distortion=distortion, separation=separation)
+    flags = dict(quality=quality, distortion=distortion, separation=separation)
+    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended, **flags)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -987,32 +954,25 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
                        "snr": float(table[sid, 1])}
         out["baseline"]["stoi"] = bstoi
         out["improvements"]["stoi"] = sscore - bstoi
-    if quality:
-        base_q = None
-        for k, name in enumerate(("segsnr", "fwsegsnr")):
+    for f, base_fn in ((FAMILIES["quality"], quality_fn), (FAMILIES["distortion"], distortion_fn)):
+        if not flags[f.flag]:
+            continue
+        base = None
+        for k, name in enumerate(f.names):
             out[name] = None
             qid, qscore = select_best(specs, table, name)[(0, alg)]
             if qid < 0:
                 continue
-            if base_q is None:
-                base_q = (quality_fn or _device_quality)(clean[0], noisy[0], sr)
+            if base is None:
+                base = base_fn(clean[0], noisy[0], sr) if base_fn else \
+                    _device_scores(f.names, clean[0], noisy[0], sr)
             out[name] = {"score": qscore, "params": dict(specs[qid][2]), "cell": int(qid),
                          "snr": float(table[qid, 1])}
-            out["baseline"][name] = base_q[k] or 0
-            out["improvements"][name] = qscore - out["baseline"][name]
-    if distortion:
-        base_d = None
-        for k, name in enumerate(("llr", "cep")):
-            out[name] = None
-            did, dscore = select_best(specs, table, name)[(0, alg)]
-            if did < 0:
-                continue
-            if base_d is None:
-                base_d = (distortion_fn or _device_distortion)(clean[0], noisy[0], sr)
-            out[name] = {"score": dscore, "params": dict(specs[did][2]), "cell": int(did),
-                         "snr": float(table[did, 1])}
-            out["baseline"][name] = base_d[k] or 0
-            out["improvements"][name] = out["baseline"][name] - dscore
+            b = out["baseline"][name] = base[k] or 0
+            out["improvements"][name] = qscore - b if f.sign > 0 else b - qscore
+    # separation stays written out: each of its entries carries the other two
+    # scores of its cell, and its baseline function returns one score, not one
+    # per name, which no record field says
     if separation:
         for name in SEPARATION_COLUMNS:
             out[name] = None
@@ -1024,7 +984,8 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
             out[name].update({k: _finite(table[pid, c]) for k, c in SEPARATION_COLUMNS.items()
                               if k != name})
             if name == "sisdr":
-                base_p = (separation_fn or _device_separation)(clean[0], noisy[0], sr)
+                base_p = separation_fn(clean[0], noisy[0], sr) if separation_fn else \
+                    _device_scores((name,), clean[0], noisy[0], sr)[0]
                 out["baseline"][name] = base_p or 0
                 out["improvements"][name] = pscore - out["baseline"][name]
     return out
@@ -1065,22 +1026,20 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     summary_means.json)."""
     import torch
     import torch.distributed as dist
-    from . import results
+    from . import metrics, results
     from .engine import Engine
-    from .metrics import LpcPlan, SegSnrPlan, SiSdrPlan, StoiPlan, WssPlan
     grids = grids or ALGORITHM_GRIDS
     algorithms = list(algorithms or grids)
     specs = job_specs(len(noisy), algorithms, grids)
+    flags = dict(quality=quality, distortion=distortion, separation=separation, wss=wss)
+    fams = scores.requested(**flags)
     table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
-                           quality=quality, distortion=distortion, separation=separation, wss=wss)
+                           **flags)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
     best_stoi = select_best(specs, table, "stoi")
-    best_fw = select_best(specs, table, "fwsegsnr") if quality else None
-    best_llr = select_best(specs, table, "llr") if distortion else None
-    best_sdr = select_best(specs, table, "sisdr") if separation else None
-    best_wss = select_best(specs, table, "wss") if wss else None
+    best_lead = {f.flag: select_best(specs, table, f.lead) for f in fams}
     eng = Engine()
     rows = []
     for pair, stem in enumerate(stems):
@@ -1088,25 +1047,15 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         n = np.asarray(noisy[pair], np.float64)
         snr_noisy = _snr_baseline(c, n)
         m = min(len(c), len(n))
-        plan = StoiPlan(torch.as_tensor(c[:m]).cuda().view(1, -1), extended=extended)
+        plan = metrics.StoiPlan(torch.as_tensor(c[:m]).cuda().view(1, -1), extended=extended)
         nf = torch.as_tensor(n[:m].astype(np.float32)).cuda()
         stoi_noisy = _opt(plan.score(nf, [0], [0], clip=False)[0])
-        q_noisy = None
-        if quality:
-            qplan = SegSnrPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
-            q_noisy = [_opt(v) for v in qplan.score(nf, [0], [0], clip=False)[0]]
-        d_noisy = None
-        if distortion:
-            dplan = LpcPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
-            d_noisy = [_opt(v) for v in dplan.score(nf, [0], [0], clip=False)[0]]
-        p_noisy = None
-        if separation:
-            pplan = SiSdrPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
-            p_noisy = _finite(pplan.score(nf, [0], [0], clip=False)[0, 0])
-        w_noisy = None
-        if wss:
-            wplan = WssPlan(torch.as_tensor(c[:m]).cuda().view(1, -1))
-            w_noisy = _opt(wplan.score(nf, [0], [0], clip=False)[0])
+        noisy_kw = {}  # per family, the unprocessed input's <name>_noisy of its baselines
+        for f in fams:
+            fplan = getattr(metrics, f.plan)(torch.as_tensor(c[:m]).cuda().view(1, -1))
+            v = np.atleast_1d(fplan.score(nf, [0], [0], clip=False)[0])
+            noisy_kw[f.flag] = {f"{name}_noisy": (_finite if f.finite_only else _opt)(
+                v[f.names.index(name)]) for name in f.baselines}
         x = torch.as_tensor(n).cuda().view(1, -1)
         cl = torch.as_tensor(c).cuda().view(1, -1)
         for alg in algorithms:
@@ -1116,12 +1065,22 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
             sid, sscore = best_stoi[(pair, alg)]
             out_dir = os.path.join(out_root, f"results_{alg}")
             os.makedirs(out_dir, exist_ok=True)
-            fid, fscore = best_fw[(pair, alg)] if quality else (-1, None)
-            lid, lscore = best_llr[(pair, alg)] if distortion else (-1, None)
-            pid, pscore = best_sdr[(pair, alg)] if separation else (-1, None)
-            wid, wscore = best_wss[(pair, alg)] if wss else (-1, None)
-            for tag, k in (("snr", cid), ("stoi", sid), ("fwsegsnr", fid), ("llr", lid),
-                           ("sisdr", pid), ("wss", wid)):
+            written, family_kw = [("snr", cid), ("stoi", sid)], {}
+            for f in fams:
+                k, kscore = best_lead[f.flag][(pair, alg)]
+                written.append((f.lead, k))
+                conv = _finite if f.finite_only else _opt
+                family_kw.update(noisy_kw[f.flag])
+                family_kw.update({
+                    f"{f.lead}_best": None if k < 0 else float(kscore),
+                    f"{f.lead}_params": None if k < 0 else specs[k][2],
+                    f"snr_{f.tag}opt": None if k < 0 else float(table[k, 1])})
+                # the winner's other scores, for the families whose rows have them
+                family_kw.update({
+                    f"{name}_{f.tag}opt": None if k < 0 else conv(table[k, col])
+                    for name, col in scores.columns(f).items()
+                    if f"{name}_{f.tag}opt" in f.row_args})
+            for tag, k in written:
                 if k < 0:
                     continue
                 res = eng.run(x, [(0, alg, specs[k][2])], clean=cl, want_waveforms=True, align=True)
@@ -1133,29 +1092,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                 stem, alg, sr, snr_noisy, float(score), specs[cid][2], stoi_noisy=stoi_noisy,
                 stoi_best=None if sid < 0 else float(sscore),
                 stoi_params=None if sid < 0 else specs[sid][2],
-                snr_stoiopt=None if sid < 0 else float(table[sid, 1]),
-                **({} if not quality else dict(
-                    segsnr_noisy=q_noisy[0], fwsegsnr_noisy=q_noisy[1],
-                    fwsegsnr_best=None if fid < 0 else float(fscore),
-                    fwsegsnr_params=None if fid < 0 else specs[fid][2],
-                    snr_fwsegopt=None if fid < 0 else float(table[fid, 1]))),
-                **({} if not distortion else dict(
-                    llr_noisy=d_noisy[0], cep_noisy=d_noisy[1],
-                    llr_best=None if lid < 0 else float(lscore),
-                    llr_params=None if lid < 0 else specs[lid][2],
-                    snr_llropt=None if lid < 0 else float(table[lid, 1]))),
-                **({} if not separation else dict(
-                    sisdr_noisy=p_noisy,
-                    sisdr_best=None if pid < 0 else float(pscore),
-                    sisir_sisdropt=None if pid < 0 else _finite(table[pid, NCOL + 5]),
-                    sisar_sisdropt=None if pid < 0 else _finite(table[pid, NCOL + 6]),
-                    sisdr_params=None if pid < 0 else specs[pid][2],
-                    snr_sisdropt=None if pid < 0 else float(table[pid, 1]))),
-                **({} if not wss else dict(
-                    wss_noisy=w_noisy,
-                    wss_best=None if wid < 0 else float(wscore),
-                    wss_params=None if wid < 0 else specs[wid][2],
-                    snr_wssopt=None if wid < 0 else float(table[wid, 1])))))
+                snr_stoiopt=None if sid < 0 else float(table[sid, 1]), **family_kw))
             if extended:
                 rows[-1]["stoi_extended"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
