@@ -1,7 +1,8 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
-include/cse_wss.h, include/cse_sisdr.h and include/cse_logerr.h).
+include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h and
+include/cse_csii.h).
 
 Entry points that share a signature are declared in one loop: the noise
 trackers (TRACKER_EXPORTS) and the waveform scores on the segSNR interface
@@ -145,6 +146,11 @@ EXPORTS_SISDR = ("cse_sisdr_workspace_bytes", "cse_sisdr_prepare", "cse_sisdr_sc
 # include/cse_logerr.h (noise-PSD logarithmic estimation error), likewise
 EXPORTS_LOGERR = ("cse_logerr_default_params", "cse_logerr_reference", "cse_logerr_scratch_bytes",
                   "cse_logerr_rows")
+# include/cse_csii.h (three-level CSII and I3): the segSNR interface with one
+# output pointer, [n_cells][4]; no record of CELL_SCORES, whose names are the
+# optional score families'
+EXPORTS_CSII = ("cse_csii_workspace_bytes", "cse_csii_prepare", "cse_csii_scratch_bytes",
+                "cse_csii_cells")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -248,6 +254,12 @@ def load(path=LIB_PATH):
         prepare.argtypes = [P, i64, i64, i32, P, P]
         # the test signals and their indices, the plan, scratch, the outputs, the stream
         cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P] + [P] * n_out + [P]
+    lib.cse_csii_workspace_bytes.restype = lib.cse_csii_scratch_bytes.restype = i64
+    lib.cse_csii_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cse_csii_scratch_bytes.argtypes = [i64, i64, i32]
+    lib.cse_csii_prepare.restype = lib.cse_csii_cells.restype = i32
+    lib.cse_csii_prepare.argtypes = [P, i64, i64, i32, P, P]
+    lib.cse_csii_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
     lib.cse_sisdr_workspace_bytes.restype = i64
     lib.cse_sisdr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_sisdr_prepare.restype = i32

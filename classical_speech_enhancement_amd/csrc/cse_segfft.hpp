@@ -1,6 +1,6 @@
 // The frame transform of the critical-band scores: what cse_segsnr.hip
-// (fwSegSNR) and cse_wss.hip (WSS) share.  Both take the 30-ms frames of
-// include/cse_segsnr.h, one wave per frame: the NFFT-point transform of the
+// (fwSegSNR), cse_wss.hip (WSS) and cse_csii.hip (CSII) share.  All take the
+// 30-ms frames of include/cse_segsnr.h, one wave per frame: the NFFT-point transform of the
 // zero-padded windowed frame and the 25 critical-band sums over the filter
 // supports.  The comments at the head of cse_segsnr.hip describe the scheme.
 #ifndef CSE_SEGFFT_HPP_
@@ -237,6 +237,25 @@ __device__ __forceinline__ void wave_powers(cx<T>* buf, const Twiddles<T, H>& tw
     wave_sync();
 }
 
+// FFT_NFFT(f)[k] itself for the lane's bins k = lane + 64 r, kept complex in
+// registers (cse_csii.hip's cross spectrum).  buf is only read: the caller
+// orders its next write to buf after this with wave_sync.
+template <typename T, int H>
+__device__ __forceinline__ void wave_split(const cx<T>* buf, const Twiddles<T, H>& tw, int lane,
+                                           cx<T> (&f)[Cfg<H>::R]) {
+    using C = Cfg<H>;
+#pragma unroll
+    for (int r = 0; r < C::R; ++r) {
+        const int k = lane + 64 * r;
+        const cx<T> a = buf[pad(k)];
+        cx<T> b = buf[pad((H - k) & (H - 1))];
+        b.y = -b.y;
+        const cx<T> e = a + b, d = mul_mi(a - b);       // 2 E[k], 2 O[k]
+        const cx<T> g = e + tw.st0 * (Twiddles<T, H>::step(r) * d);
+        f[r] = {(T)0.5 * g.x, (T)0.5 * g.y};
+    }
+}
+
 // the band's filter row times the magnitudes: lanes l and l + 32 sum half of
 // the support of band l each (l < 25); both end up with the whole sum
 template <typename T>
@@ -301,6 +320,34 @@ static inline bool band_supports(int H, Bands* b) {
         b->n[i] = hi - lo + 1;  // lo + n <= H by construction
     }
     return true;
+}
+
+// the supports of a rate, made once (12,800 exponentials on the host); NULL
+// when a row is wider than its room
+static inline const Bands* band_table(int H) {
+    struct Table {
+        Bands b;
+        bool ok;
+        explicit Table(int h) { ok = band_supports(h, &b); }
+    };
+    static const Table t512(512), t256(256);
+    const Table& t = H == 512 ? t512 : t256;
+    return t.ok ? &t.b : nullptr;
+}
+
+// the filter rows over their supports, and the supports, into LDS (fv:
+// NB * FWP entries, flo and fn: 32), by nt threads
+template <typename T>
+__device__ __forceinline__ void stage_filters(const Bands& bands, int H, T* fv, int* flo, int* fn,
+                                              int tid, int nt) {
+    if (tid < 32) {
+        flo[tid] = tid < NB ? bands.lo[tid] : 0;
+        fn[tid] = tid < NB ? bands.n[tid] : 0;
+    }
+    for (int e = tid; e < NB * FW; e += nt) {
+        const int i = e / FW, c = e % FW;
+        fv[i * FWP + c] = c < bands.n[i] ? (T)filter_entry(i, bands.lo[i] + c, H) : (T)0;
+    }
 }
 
 }  // namespace seg

@@ -43,6 +43,15 @@ cse_wss_cells).  With it the device delivers every ingredient of Hu & Loizou's
 composite measures but PESQ: composite() takes the caller's PESQ values with
 LLR, WSS and segSNR and returns CSIG, CBAK and COVL.
 
+CsiiPlan scores the three-level coherence speech intelligibility index of
+include/cse_csii.h (Kates & Arehart 2005) and its fit I3, the intelligibility
+measure Ma, Hu & Loizou (2009) found to predict best for this project's
+algorithm families, through the same interface (cse_csii_prepare /
+cse_csii_cells): four values per cell, higher is better.  It is no score family
+(scores.FAMILIES): like extended STOI it can take STOI's place as the sweep's
+intelligibility column (search: coherence=True), and evaluate_audio_quality adds
+it on request (coherence=True).
+
 SiSdrPlan scores the scale-invariant SDR of include/cse_sisdr.h (Le Roux et al.
 2019) and, when the batch's noisy signals are given, its split into SI-SIR
 (residual interference) and SI-SAR (artifacts) through cse_sisdr_prepare /
@@ -349,6 +358,48 @@ class WssPlan(SegSnrPlan):
         return self.score_async(y, y_offset, sig_of, lag, clip).cpu().numpy()
 
 
+class CsiiPlan(SegSnrPlan):
+    """Clean side of the three-level CSII and I3 (include/cse_csii.h) for S
+    equal-length signals at 16 or 8 kHz: SegSnrPlan's construction, checks and
+    launch chunking on cse_csii_prepare / cse_csii_cells, with four values per
+    cell (csii_high, csii_mid, csii_low, i3; higher is better).  A level with no
+    frame scores NaN, and I3 is NaN when the mid or the low level has none."""
+
+    _PREFIX = "cse_csii"
+    _LABEL = "CSII"
+    _WHICH = ("csii_high", "csii_mid", "csii_low", "i3")
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True, out=None, which="all"):
+        """Enqueue the four values of every cell; returns the [n, 4] f64 cuda
+        result.  The arguments are SegSnrPlan.score_async's.  which="i3" (or
+        another name of _WHICH) returns that column alone, [n]; the kernel
+        computes all four either way."""
+        if which != "all" and which not in self._WHICH:
+            raise ValueError(f"which={which!r}: 'all' or one of {self._WHICH}")
+        off, sig, lg, n = _cell_index(self, y, y_offset, sig_of, lag)
+        dev = self.clean.device
+        if which != "all":
+            table = torch.empty((n, 4), dtype=torch.float64, device=dev)
+            self._launch(y, off, sig, lg, n, clip, (table,))
+            col = table[:, self._WHICH.index(which)]
+            if out is None:
+                return col.contiguous()
+            if out.shape != (n,) or out.dtype != torch.float64:
+                raise ValueError("out must be a [n] float64 tensor")
+            out.copy_(col)
+            return out
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        if out.shape != (n, 4) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n, 4] float64 tensor")
+        self._launch(y, off, sig, lg, n, clip, (out,))
+        return out
+
+    def score(self, y, y_offset, sig_of, lag=None, clip=True, which="all"):
+        """score_async, synchronised: [n, 4] numpy (or [n] for one column)."""
+        return self.score_async(y, y_offset, sig_of, lag, clip, which=which).cpu().numpy()
+
+
 class SiSdrPlan:
     """Clean side of SI-SDR / SI-SIR / SI-SAR (include/cse_sisdr.h) for S
     equal-length signals (clean: [S, L] f64 cuda, any rate).  noisy ([S, L] f64
@@ -612,6 +663,47 @@ def wss(x, y, fs):
     return _pair_score(WssPlan, x, y, "wss", sr=fs)
 
 
+def csii(x, y, fs):
+    """(CSII_high, CSII_mid, CSII_low, I3) of y against the clean x
+    (include/cse_csii.h); higher is better.  A level without frames gives NaN,
+    and so does I3 without mid or low frames."""
+    x, y = _pair_signals(x, y, "csii")
+    plan = CsiiPlan(torch.as_tensor(x).cuda().view(1, -1), sr=fs)
+    yd = torch.as_tensor(y.astype(np.float32)).cuda()
+    return tuple(float(v) for v in plan.score(yd, [0], [0], clip=False)[0])
+
+
+def calculate_csii(clean_reference, test_audio, sr):
+    """I3 with calculate_stoi's shape: trim to the common length, None on
+    failure (a clip with no mid-level or no low-level frame included)."""
+    def fn(x, y, fs):
+        v = csii(x, y, fs)[3]
+        if math.isnan(v):
+            raise ValueError("I3 is undefined (no mid-level or no low-level 30-ms frame)")
+        return v
+    return _calculate_quality(fn, "CSII", clean_reference, test_audio, sr)
+
+
+def _coherence(clean_reference, noisy_audio, enhanced_audio, sr):
+    """csii_high_*, csii_mid_*, csii_low_* (noisy, enhanced) and i3_noisy,
+    i3_enhanced, i3_improvement; {} on failure."""
+    try:
+        n = min(len(clean_reference), len(noisy_audio), len(enhanced_audio))
+        c = np.asarray(clean_reference)[:n]
+        v_noisy = csii(c, np.asarray(noisy_audio)[:n], sr)
+        v_enh = csii(c, np.asarray(enhanced_audio)[:n], sr)
+        out = {}
+        for k, name in enumerate(CsiiPlan._WHICH):
+            out[f"{name}_noisy"], out[f"{name}_enhanced"] = v_noisy[k], v_enh[k]
+        out["i3_improvement"] = v_enh[3] - v_noisy[3]
+        return out
+    except (NotImplementedError, _lib.CseError):
+        raise  # no device / unsupported: not a score failure
+    except Exception as e:  # calculate_stoi's catch-all
+        print(f"CSII calculation failed: {e}")
+        return {}
+
+
 def composite(pesq, llr, wss, segsnr):
     """(CSIG, CBAK, COVL): Hu & Loizou's (2008) composite predictions of the
     signal-distortion, background-intrusiveness and overall-quality ratings, the
@@ -756,13 +848,17 @@ def _separation(clean_reference, noisy_audio, enhanced_audio):
 
 
 def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name="",
-                           quality=False, distortion=False, separation=False, wss=False):
+                           quality=False, distortion=False, separation=False, wss=False,
+                           coherence=False):
     """evaluation_metrics.evaluate_audio_quality (:61-101), same keys;
     quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement);
     distortion=True adds llr_* and cep_* likewise, their improvement being
     noisy - enhanced (lower is better); separation=True adds sisdr_enhanced,
     sisir_enhanced and sisar_enhanced, and sisdr_noisy with sisdr_improvement;
-    wss=True adds wss_noisy, wss_enhanced and wss_improvement (noisy - enhanced)."""
+    wss=True adds wss_noisy, wss_enhanced and wss_improvement (noisy - enhanced);
+    coherence=True adds csii_high_*, csii_mid_* and csii_low_* (noisy, enhanced)
+    and i3_noisy, i3_enhanced and i3_improvement (include/cse_csii.h; a level
+    without frames gives NaN)."""
     results = {}
     s_noisy = calculate_stoi(clean_reference, noisy_audio, sr)
     s_enh = calculate_stoi(clean_reference, enhanced_audio, sr)
@@ -791,6 +887,8 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
                 results[f"{key}_noisy"] = v_noisy
                 results[f"{key}_enhanced"] = v_enh
                 results[f"{key}_improvement"] = v_enh - v_noisy if f.sign > 0 else v_noisy - v_enh
+    if coherence:
+        results.update(_coherence(clean_reference, noisy_audio, enhanced_audio, sr))
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:
@@ -809,4 +907,7 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     if "sisdr_enhanced" in results:
         print(f"SI-SDR: {results['sisdr_noisy']:.2f} -> {results['sisdr_enhanced']:.2f} dB "
               f"(SI-SIR {results['sisir_enhanced']:.2f}, SI-SAR {results['sisar_enhanced']:.2f})")
+    if "i3_noisy" in results:
+        print(f"I3: {results['i3_noisy']:.4f} -> {results['i3_enhanced']:.4f} (CSII mid "
+              f"{results['csii_mid_noisy']:.4f} -> {results['csii_mid_enhanced']:.4f})")
     return results

@@ -39,6 +39,15 @@ engine_compute) scores extended STOI in place of STOI (cse_estoi_cells,
 include/cse_estoi.h): the STOI column and every stoi field then hold ESTOI, and
 the selection and its tolerance are the STOI objective's.
 
+coherence=True (run_grid, optimize_parameters, run_sweep; stoi="coherence" in
+engine_compute) scores I3, the fit of the three-level coherence speech
+intelligibility index (cse_csii_cells, include/cse_csii.h; Kates & Arehart
+2005), in place of STOI in exactly the same way: the STOI column and every stoi
+field then hold I3, and the selection and its tolerance are the STOI
+objective's.  A clip with no mid-level or no low-level frame has no I3: its
+cells hold NaN in the column and the scan skips them, like any cell without a
+score.  extended and coherence exclude each other.
+
 quality=True (engine_compute, run_grid, optimize_parameters, run_sweep) adds the
 quality objective the reference takes from PESQ: segmental SNR and
 frequency-weighted segmental SNR (cse_segsnr_cells, include/cse_segsnr.h;
@@ -72,7 +81,7 @@ tables, the selection, the sweep's per-family work and the result rows loop
 over the records, and the per-family constants below (QUALITY_COLUMNS, ...) are
 derived from them.  The public signatures keep one keyword per family and pass
 the requested records, or the dict of flags, down.  STOI is no family: it owns
-column 3 of every table and the extended switch.
+column 3 of every table and the extended and coherence switches.
 
 score_noise_estimators and sweep_tracker judge noise-PSD estimates themselves,
 with no enhancement algorithm on top: the logarithmic estimation error of
@@ -350,7 +359,9 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     """Device compute of the cells ``ids``: per-cell (sse, snr, finite, stoi,
     lag, xstatus), scored after finalize_enhanced's alignment (align=False: at
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
-    waveforms are kept); stoi="extended" fills it with extended STOI.
+    waveforms are kept); stoi="extended" fills it with extended STOI,
+    stoi="coherence" with the CSII's I3 (include/cse_csii.h; NaN for a clip
+    without mid-level or low-level frames).
     quality=True appends segsnr and fwsegsnr (QUALITY_COLUMNS; NaN where the
     cell is not finite), scored on the side stream from the same waveforms,
     with or without STOI.  distortion=True makes the rows NCOL + 4 wide and
@@ -377,8 +388,8 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     and trims the cache back to
     the caller's size on return."""
     from .engine import Engine
-    if not (isinstance(stoi, bool) or stoi == "extended"):
-        raise ValueError(f"stoi={stoi!r}: True, False or 'extended'")
+    if not (isinstance(stoi, bool) or stoi in ("extended", "coherence")):
+        raise ValueError(f"stoi={stoi!r}: True, False or 'extended' (or 'coherence')")
     own = engine is None
     eng = engine or Engine()
     size0 = eng.plan_cache_size
@@ -392,6 +403,24 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
             eng.plan_cache_size = size0
             while len(eng._plan_cache) > max(size0, 1):
                 eng._plan_cache.popitem(last=False)
+
+
+class _I3Column:
+    """metrics.CsiiPlan behind the one-column score_async the sweep calls: I3."""
+
+    def __init__(self, clean):
+        from . import metrics
+        self.plan = metrics.CsiiPlan(clean)
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True):
+        return self.plan.score_async(y, y_offset, sig_of, lag=lag, clip=clip, which="i3")
+
+
+def _stoi_switch(extended, coherence):
+    """engine_compute's stoi= of the two switches, which exclude each other."""
+    if extended and coherence:
+        raise ValueError("extended and coherence both fill the STOI column: choose one")
+    return "extended" if extended else ("coherence" if coherence else True)
 
 
 def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, fams=()):
@@ -465,7 +494,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, fams=()):
                                           np.asarray(clean[p], np.float64))) for p in pairs])
             # (first column, plan) in launch order: STOI, which is no family (it
             # owns column 3), then the requested families in registry order
-            plans = [(TABLE_COLUMN["stoi"],
+            plans = [(TABLE_COLUMN["stoi"], _I3Column(cl) if stoi == "coherence" else
                       metrics.StoiPlan(cl, extended=(stoi == "extended")))] if stoi else []
             for f in fams:
                 cls = getattr(metrics, f.plan)
@@ -714,14 +743,16 @@ def _select_best(specs, table, objective, tol):
 
 
 def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
-             extended=False, quality=False, distortion=False, separation=False, wss=False):
+             extended=False, quality=False, distortion=False, separation=False, wss=False,
+             coherence=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
     gets the full table (all_gather); the selection is the deterministic
     sequential scan, identical on every rank.  extended=True: the default
     compute (engine_compute) scores extended STOI into the stoi column; a
-    compute function given by the caller scores what it scores.  quality=True:
+    compute function given by the caller scores what it scores.  coherence=True:
+    likewise with the CSII's I3 (not together with extended).  quality=True:
     the table has NCOL + 2 columns (QUALITY_COLUMNS: segsnr, fwsegsnr), filled
     by the default compute; a caller's compute function returns them itself.
     distortion=True: NCOL + 4 columns (the quality columns, NaN without
@@ -731,6 +762,7 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     wss=True: NCOL + 8 columns (all of those, NaN unless asked for, then
     WSS_COLUMNS: wss), likewise."""
     import torch.distributed as dist
+    stoi_kind = _stoi_switch(extended, coherence)
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
     rank = dist.get_rank(group) if dist_on else 0
@@ -740,10 +772,9 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     flags = dict(quality=quality, distortion=distortion, separation=separation, wss=wss)
     fams = scores.requested(**flags)
     ncol = _width(fams)
-    if compute is None and (extended or fams):
+    if compute is None and (extended or coherence or fams):
         def compute(clean, noisy, specs, ids):
-            return engine_compute(clean, noisy, specs, ids,
-                                  stoi="extended" if extended else True, **flags)
+            return engine_compute(clean, noisy, specs, ids, stoi=stoi_kind, **flags)
     compute = compute or engine_compute
     vals = compute(clean, noisy, specs, ids) if len(ids) else np.zeros((0, ncol))
     if np.ndim(vals) != 2 or np.shape(vals)[1] != ncol:
@@ -876,8 +907,10 @@ def _snr_baseline(c, n):
     return math.inf if err == 0 else float(10 * np.log10(np.sum(c[:m] ** 2) / (err + 1e-10)))
 
 
-def _device_stoi(clean, test, sr, extended=False):
-    from .metrics import calculate_stoi
+def _device_stoi(clean, test, sr, extended=False, coherence=False):
+    from .metrics import calculate_csii, calculate_stoi
+    if coherence:
+        return calculate_csii(clean, test, sr)
     return calculate_stoi(clean, test, sr, extended=extended)
 
 
@@ -900,7 +933,7 @@ def _finite(v):
 def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_ranges=None,
                         compute=None, stoi_fn=None, extended=False, quality=False,
                         quality_fn=None, distortion=False, distortion_fn=None, separation=False,
-                        separation_fn=None):
+                        separation_fn=None, coherence=False):
     """Single-pair, single-algorithm mirror of the reference's
     optimize_parameters (speech_enhancement_comparison.py:109-252), scored by
     STOI and SNR: returns {'stoi': {'score', 'params', 'cell', 'snr'},
@@ -911,6 +944,8 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     extended=True: the cells and the baseline are scored with extended STOI
     (every 'stoi' value above is then ESTOI) and the result carries
     'extended': True.
+    coherence=True: likewise with the CSII's I3 (include/cse_csii.h; every
+    'stoi' value is then I3) and 'coherence': True; not together with extended.
     quality=True: the table has the two quality columns and the result gains
     'segsnr' and 'fwsegsnr' entries shaped like 'stoi' ({'score', 'params',
     'cell', 'snr'}, None when no cell has the score), with their baselines
@@ -933,7 +968,8 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     clean = [np.asarray(clean_reference, np.float64)]
     noisy = [np.asarray(noisy_audio, np.float64)]
     flags = dict(quality=quality, distortion=distortion, separation=separation)
-    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended, **flags)
+    table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended,
+                           coherence=coherence, **flags)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -944,10 +980,13 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
            "stoi": None}
     if extended:
         out["extended"] = True
+    if coherence:
+        out["coherence"] = True
     sid, sscore = select_best(specs, table, "stoi")[(0, alg)]
     if sid >= 0:
-        if stoi_fn is None and extended:
-            bstoi = _device_stoi(clean[0], noisy[0], sr, extended=True) or 0
+        if stoi_fn is None and (extended or coherence):
+            bstoi = _device_stoi(clean[0], noisy[0], sr, extended=extended,
+                                 coherence=coherence) or 0
         else:
             bstoi = (stoi_fn or _device_stoi)(clean[0], noisy[0], sr) or 0  # :115 "or 0"
         out["stoi"] = {"score": sscore, "params": dict(specs[sid][2]), "cell": int(sid),
@@ -993,7 +1032,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
               group=None, device=None, extended=False, quality=False, distortion=False,
-              separation=False, wss=False):
+              separation=False, wss=False, coherence=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
@@ -1004,6 +1043,11 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     extended=True: scored and selected by extended STOI; the rows' stoi_* fields
     then hold ESTOI, each row carries "stoi_extended": True, and the file names
     stay the same.
+    coherence=True: scored and selected by the CSII's I3 (include/cse_csii.h) in
+    the same way; the rows' stoi_* fields then hold I3, each row carries
+    "stoi_coherence": True, the noisy baseline is metrics.CsiiPlan's, and the
+    file names stay the same.  A pair without mid-level or low-level frames has
+    no I3: its stoi fields are None.  Not together with extended.
     quality=True: the cells are also scored by segSNR and fwSegSNR; the
     fwSegSNR-best cell's waveform is written as ..._optimized_fwsegsnr.wav and
     each row gains segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best,
@@ -1034,7 +1078,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     flags = dict(quality=quality, distortion=distortion, separation=separation, wss=wss)
     fams = scores.requested(**flags)
     table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
-                           **flags)
+                           coherence=coherence, **flags)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
@@ -1047,9 +1091,10 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         n = np.asarray(noisy[pair], np.float64)
         snr_noisy = _snr_baseline(c, n)
         m = min(len(c), len(n))
-        plan = metrics.StoiPlan(torch.as_tensor(c[:m]).cuda().view(1, -1), extended=extended)
+        cm = torch.as_tensor(c[:m]).cuda().view(1, -1)
+        plan = _I3Column(cm) if coherence else metrics.StoiPlan(cm, extended=extended)
         nf = torch.as_tensor(n[:m].astype(np.float32)).cuda()
-        stoi_noisy = _opt(plan.score(nf, [0], [0], clip=False)[0])
+        stoi_noisy = _opt(float(plan.score_async(nf, [0], [0], clip=False).cpu()[0]))
         noisy_kw = {}  # per family, the unprocessed input's <name>_noisy of its baselines
         for f in fams:
             fplan = getattr(metrics, f.plan)(torch.as_tensor(c[:m]).cuda().view(1, -1))
@@ -1095,5 +1140,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                 snr_stoiopt=None if sid < 0 else float(table[sid, 1]), **family_kw))
             if extended:
                 rows[-1]["stoi_extended"] = True
+            if coherence:
+                rows[-1]["stoi_coherence"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
     return rows
