@@ -64,6 +64,18 @@ def route(n_fft, hop):
     return None
 
 
+def route_refusal(n_fft, hop):
+    """Why route(n_fft, hop) is None, one reason per message: an odd n_fft (the
+    reference's istft rejects it too), an n_fft outside [64, 4096], or a hop
+    outside [1, n_fft]."""
+    n_fft, hop = int(n_fft), int(hop)
+    if n_fft % 2:
+        return f"engine supports an even n_fft only (got n_fft={n_fft})"
+    if not 64 <= n_fft <= 4096:
+        return f"engine supports n_fft in [64, 4096] (got n_fft={n_fft})"
+    return f"engine supports hop in [1, n_fft] (got n_fft={n_fft}, hop={hop})"
+
+
 def n_frames(length, hop):
     return 1 + int(length) // int(hop)
 
@@ -170,8 +182,7 @@ def specs_by_n_fft(S, L, specs, with_clean, want_g):
         if ck not in checked:  # per distinct (algorithm, hop, n_fft, method)
             r = route(nf, hop)
             if r is None:
-                raise ValueError(f"engine supports an even n_fft in [64, 4096] and "
-                                 f"hop in [1, n_fft] (got n_fft={nf}, hop={hop})")
+                raise ValueError(route_refusal(nf, hop))
             if want_g and r == SHORT:
                 raise ValueError(f"gain matrices not at the short hops (n_fft={nf}, hop={hop})")
             noise_key(alg, p, n_frames(L, hop))  # validates the method

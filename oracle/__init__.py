@@ -17,7 +17,8 @@ Pinning status:
     (≈1e-2 rel-L2, limited by resampler substitution + PCM16).
 """
 
-from .stft_ref import stft, istft, fix_length, hann_periodic, n_frames_for
+from .stft_ref import (stft, istft, fix_length, hann_periodic, n_frames_for,
+                       window_sumsquare)
 from .noise_ref import (noise_estimation, percentile_noise, min_tracking_noise,
                         true_noise, simple_noise)
 from .gain_ref import (spectral_subtraction, wiener_filter, mmse, advanced_mmse,
@@ -27,7 +28,8 @@ from .pipeline_ref import (GRIDS, grid_cells, finalize_enhanced, calculate_snr,
                            combined_score, tolerance_scan)
 
 __all__ = [
-    "stft", "istft", "fix_length", "hann_periodic", "n_frames_for", "align_lag",
+    "stft", "istft", "fix_length", "hann_periodic", "n_frames_for", "window_sumsquare",
+    "align_lag",
     "noise_estimation", "percentile_noise", "min_tracking_noise", "true_noise",
     "simple_noise", "spectral_subtraction", "wiener_filter", "mmse",
     "advanced_mmse", "ALGORITHMS", "GRIDS", "grid_cells", "finalize_enhanced",

@@ -95,3 +95,28 @@ def test_structure_digest_and_fingerprint():
     s1 = [(0, "wiener", p), (1, "mmse", q)]
     assert spec_fingerprint(s1) == spec_fingerprint(list(s1))
     assert spec_fingerprint(s1) != spec_fingerprint([(0, "wiener", p), (1, "mmse", p)])
+
+
+def test_route_refusals_name_their_reason():
+    """A shape no kernel runs is refused with the one reason that applies: an
+    odd n_fft, an n_fft outside [64, 4096], a hop outside [1, n_fft]
+    (the device twin: test_gpu_parity.test_unknown_method_and_missing_clean_raise)."""
+    import pytest
+    from classical_speech_enhancement_amd import layout
+    p = dict(alpha=0.95, gain_floor=0.05, noise_percentile=10.0, noise_method="percentile")
+
+    def plan(n_fft, hop):
+        return layout.specs_by_n_fft(1, 8000, [(0, "wiener", dict(p, n_fft=n_fft, hop_length=hop))],
+                                     False, False)
+    for n_fft, hop, why in ((511, 128, "even n_fft"), (401, 160, "even n_fft"),
+                            (63, 16, "even n_fft"), (8192, 1024, r"n_fft in \[64, 4096\]"),
+                            (62, 16, r"n_fft in \[64, 4096\]"), (4098, 16, r"n_fft in \[64, 4096\]"),
+                            (512, 0, r"hop in \[1, n_fft\]"), (512, 513, r"hop in \[1, n_fft\]"),
+                            (1024, 2048, r"hop in \[1, n_fft\]"), (64, -1, r"hop in \[1, n_fft\]")):
+        assert layout.route(n_fft, hop) is None
+        with pytest.raises(ValueError, match="engine supports .*" + why) as e:
+            plan(n_fft, hop)
+        assert sum(w in str(e.value) for w in ("even n_fft", "n_fft in [64", "hop in [1")) == 1
+    for n_fft, hop in ((64, 1), (64, 64), (4096, 4096), (4094, 2047), (512, 512)):
+        (got, items), = plan(n_fft, hop)
+        assert got == n_fft and len(items) == 1

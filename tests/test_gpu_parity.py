@@ -158,7 +158,7 @@ def test_short_hops_10s_vs_oracle(P, n_fft, hop):
 
 
 def test_generic_shapes_match_reference_golden(P):
-    """cse_enhance_cells_generic (any even n_fft in [64, 2048], any hop up to
+    """cse_enhance_cells_generic (any even n_fft in [64, 4096], any hop up to
     n_fft; here 128/32, 256/64, 512/160, 512/512, 1024/512, 2048/512 and the
     direct-DFT shapes 400/160, 320/80) through the plugins against the
     reference's outputs (float32-stored)."""
@@ -196,12 +196,53 @@ def test_generic_shapes_10s_vs_oracle(P, n_fft, hop):
         assert rel_l2(y, ref) <= TOL and rel_max(y, ref) <= TOL, (alg, rel_l2(y, ref))
 
 
-@pytest.mark.parametrize("n_fft,hop", [(400, 160), (2048, 512), (256, 64), (4096, 1024)])
+HOP1_SLICE = slice(4000, 5600)  # a voiced stretch of make_pair(4, 1.0) and make_pair(8, 2.0)
+
+
+@pytest.mark.parametrize("n_fft,hop,seconds", [(64, 16, 1.0), (64, 64, 1.0), (66, 22, 1.0),
+                                               (4000, 1000, 2.0), (4094, 2047, 2.0),
+                                               (64, 1, None), (130, 1, None)])
+def test_generic_edge_shapes_vs_oracle(P, n_fft, hop, seconds):
+    """The shapes no other test runs through the layers above the STFT: n_fft
+    64 (stft_kernel<64>, B = 33), hop = n_fft, the direct DFT at 66 and above
+    2048 (B = 2001 and 2048: the 9-bins-per-thread noise finish), and hop 1;
+    every algorithm against the fp64 oracle at the north-star tolerance, on
+    short clips so the oracle stays quick.  The hop-1 clips are 1600 samples
+    from inside a 1-s pair: its first 1600 samples are silent, so the slice
+    must hold speech (asserted).  No case is ill-conditioned in the oracle
+    itself (test_tiny_lengths' check, asserted, never skipped on)."""
+    clean, noisy = make_pair(4, seconds=seconds or 1.0)
+    if seconds is None:
+        clean, noisy = clean[HOP1_SLICE].copy(), noisy[HOP1_SLICE].copy()
+        assert len(clean) == 1600 and np.sqrt(np.mean(clean ** 2)) > 0.01
+    for alg, method in (("ss", "true_noise"), ("wiener", "percentile"),
+                        ("mmse", "min_tracking"), ("omlsa", "min_tracking")):
+        kw = dict(CELLS[alg], n_fft=n_fft, hop_length=hop, noise_percentile=10.0,
+                  noise_method=method)
+        if method == "true_noise":
+            kw["clean_audio"] = clean
+        ref = ORACLE[alg](noisy, 16000, **kw)
+        cond = rel_l2(ORACLE[alg](noisy * (1 + 1e-9), 16000, **kw), ref)
+        print(f"{n_fft}/{hop} {alg}: oracle conditioning {cond:.2e}")
+        assert cond <= 1e-6, (alg, cond)
+        y = _fn(P, alg)(noisy, 16000, **kw)
+        assert y.shape == ref.shape and np.all(np.isfinite(y))
+        assert rel_l2(y, ref) <= TOL and rel_max(y, ref) <= TOL, (alg, rel_l2(y, ref))
+
+
+@pytest.mark.parametrize("n_fft,hop", [(400, 160), (2048, 512), (256, 64), (4096, 1024),
+                                       (64, 16), (4000, 1000), (4094, 2047), (64, 1)])
 def test_noise_estimation_generic_shapes(P, n_fft, hop):
     """plugins.noise_estimation at STFT shapes beyond the grid's (the generic
-    STFT: radix 2 or, at 400, the direct DFT) against the oracle's
-    estimators; fp32 storage of fp64 estimates, rtol 1e-6."""
+    STFT: radix 2 or, at 400, 4000 and 4094, the direct DFT; B = 33, 2001 and
+    2048 bins in the noise kernels) against the oracle's estimators; fp32
+    storage of fp64 estimates, rtol 1e-6.  At hop 1 the clip is 1600 voiced
+    samples of the pair (1601 frames): the whole pair would be 32001 frames,
+    past the 16384 the estimators sort."""
     clean, noisy = make_pair(8, seconds=2.0)
+    if hop == 1:
+        clean, noisy = clean[HOP1_SLICE].copy(), noisy[HOP1_SLICE].copy()
+        assert np.sqrt(np.mean(clean ** 2)) > 0.01
     for method in ("percentile", "min_tracking", "true_noise"):
         kw = dict(method=method, n_fft=n_fft, hop_length=hop, percentile=15.0,
                   clean_audio=clean, eps=1e-10)
@@ -226,7 +267,16 @@ def test_generic_gains_and_sse_match_oracle():
              (0, "mmse", dict(CELLS["mmse"], n_fft=512, hop_length=160, noise_percentile=10.0,
                                noise_method="percentile")),
              (0, "omlsa", dict(CELLS["omlsa"], n_fft=2048, hop_length=512,
-                                noise_percentile=10.0, noise_method="min_tracking"))]
+                                noise_percentile=10.0, noise_method="min_tracking")),
+             # the direct-DFT branch (n_fft not a power of two) and the smallest n_fft
+             (0, "mmse", dict(CELLS["mmse"], n_fft=400, hop_length=160, noise_percentile=10.0,
+                               noise_method="min_tracking")),
+             (0, "wiener", dict(CELLS["wiener"], n_fft=400, hop_length=160,
+                                 noise_percentile=20.0, noise_method="percentile")),
+             (0, "omlsa", dict(CELLS["omlsa"], n_fft=64, hop_length=16, noise_percentile=10.0,
+                                noise_method="min_tracking")),
+             (0, "mmse", dict(CELLS["mmse"], n_fft=64, hop_length=16, noise_percentile=10.0,
+                               noise_method="percentile"))]
     res = eng.run(x, specs, clean=c, want_gains=True)
     for i, ((sig, alg, p), G) in enumerate(zip(specs, res["G"])):
         Y, Pw, N = gain_ref.analyse(noisy, 16000, p["n_fft"], p["hop_length"],
@@ -235,12 +285,15 @@ def test_generic_gains_and_sse_match_oracle():
         if alg == "wiener":
             ref = gain_ref.wiener_gains(Pw, np.maximum(N, 1e-10), p["alpha"], p["gain_floor"])
         elif alg == "mmse":
+            if N.ndim == 2 and N.shape[1] > 1:  # a per-frame estimate is smoothed (mmse.py:48-54)
+                N = gain_ref.smooth_noise(N, 0.98)
             ref = gain_ref.mmse_gains(Pw, N, p["alpha"], p["ksi_min"], p["gain_min"], p["gain_max"])
         else:
             Ns = gain_ref.smooth_noise(np.maximum(N, 1e-10), p["noise_mu"])
             ref = gain_ref.omlsa_gains(Pw, Ns, p["alpha"], p["ksi_min"], p["q"], p["gain_floor"])
         Gd = G.double().cpu().numpy().T
-        assert rel_l2(Gd, ref) < 1e-5, (alg, rel_l2(Gd, ref))
+        assert Gd.shape == ref.shape, (alg, p["n_fft"], Gd.shape, ref.shape)
+        assert rel_l2(Gd, ref) < 1e-5, (alg, p["n_fft"], rel_l2(Gd, ref))
         y = ORACLE[alg](noisy, 16000, **p)
         sse_ref = float(np.sum((clean - np.clip(y, -1, 1)) ** 2))
         assert abs(res["sse"][i] - sse_ref) <= 1e-5 * sse_ref, (alg, res["sse"][i], sse_ref)
@@ -312,8 +365,14 @@ def test_unknown_method_and_missing_clean_raise(P):
     # rejects the longer window (librosa ParameterError); the mirror raises too
     with pytest.raises(ValueError, match="even n_fft"):
         P.wiener_filter(noisy, 16000, 511, 128, 0.95, 0.05, 10.0, "percentile")
-    with pytest.raises(ValueError, match="even n_fft"):
-        P.mmse(noisy, 16000, 0.98, 0.01, 0.05, 1.0, 8192, 1024, 10.0, "percentile")
+    # even, but outside [64, 4096]: refused for its size (the host-side twin:
+    # test_engine_host.test_route_refusals_name_their_reason)
+    for n_fft in (8192, 62):
+        with pytest.raises(ValueError, match=r"n_fft in \[64, 4096\]"):
+            P.mmse(noisy, 16000, 0.98, 0.01, 0.05, 1.0, n_fft, 16, 10.0, "percentile")
+    for hop in (0, 513):
+        with pytest.raises(ValueError, match=r"hop in \[1, n_fft\]"):
+            P.wiener_filter(noisy, 16000, 512, hop, 0.95, 0.05, 10.0, "percentile")
 
 
 def test_gain_matrices_match_oracle_gains():
