@@ -1,8 +1,8 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
-include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h and
-include/cse_csii.h).
+include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h, include/cse_csii.h
+and include/cse_ncm.h).
 
 Entry points that share a signature are declared in one loop: the noise
 trackers (TRACKER_EXPORTS) and the waveform scores on the segSNR interface
@@ -151,6 +151,11 @@ EXPORTS_LOGERR = ("cse_logerr_default_params", "cse_logerr_reference", "cse_loge
 # optional score families'
 EXPORTS_CSII = ("cse_csii_workspace_bytes", "cse_csii_prepare", "cse_csii_scratch_bytes",
                 "cse_csii_cells")
+# include/cse_ncm.h (normalized covariance measure and its band-importance form):
+# the same interface with the exponent before the one output pointer,
+# [n_cells][2]; like CSII no record of CELL_SCORES
+EXPORTS_NCM = ("cse_ncm_workspace_bytes", "cse_ncm_prepare", "cse_ncm_scratch_bytes",
+               "cse_ncm_cells")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -260,6 +265,12 @@ def load(path=LIB_PATH):
     lib.cse_csii_prepare.restype = lib.cse_csii_cells.restype = i32
     lib.cse_csii_prepare.argtypes = [P, i64, i64, i32, P, P]
     lib.cse_csii_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
+    lib.cse_ncm_workspace_bytes.restype = lib.cse_ncm_scratch_bytes.restype = i64
+    lib.cse_ncm_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.cse_ncm_scratch_bytes.argtypes = [i64, i64, i32]
+    lib.cse_ncm_prepare.restype = lib.cse_ncm_cells.restype = i32
+    lib.cse_ncm_prepare.argtypes = [P, i64, i64, i32, P, P]
+    lib.cse_ncm_cells.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, f64, P, P]
     lib.cse_sisdr_workspace_bytes.restype = i64
     lib.cse_sisdr_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_sisdr_prepare.restype = i32

@@ -52,6 +52,17 @@ cse_csii_cells): four values per cell, higher is better.  It is no score family
 intelligibility column (search: coherence=True), and evaluate_audio_quality adds
 it on request (coherence=True).
 
+NcmPlan scores the normalized covariance measure of include/cse_ncm.h, the
+measure of the speech-transmission-index family and the other of the two best
+predictors in Ma, Hu & Loizou (2009): the squared correlation of the slow band
+envelopes of clean and test signal over the whole clip, with the fixed
+articulation-index weights (ncm) and with that study's signal-dependent
+band-importance weights, the clean band-envelope energy raised to bif_power
+(ncm_bif), through cse_ncm_prepare / cse_ncm_cells: two values per cell, higher
+is better.  Like CsiiPlan it is no score family: it can take STOI's place as the
+sweep's intelligibility column (search: modulation=True), and
+evaluate_audio_quality adds it on request (modulation=True).
+
 SiSdrPlan scores the scale-invariant SDR of include/cse_sisdr.h (Le Roux et al.
 2019) and, when the batch's noisy signals are given, its split into SI-SIR
 (residual interference) and SI-SAR (artifacts) through cse_sisdr_prepare /
@@ -400,6 +411,80 @@ class CsiiPlan(SegSnrPlan):
         return self.score_async(y, y_offset, sig_of, lag, clip, which=which).cpu().numpy()
 
 
+class NcmPlan(SegSnrPlan):
+    """Clean side of the normalized covariance measure (include/cse_ncm.h) for S
+    equal-length signals at 16 or 8 kHz: SegSnrPlan's construction, checks and
+    launch chunking on cse_ncm_prepare / cse_ncm_cells, with two values per cell
+    (ncm, with the fixed articulation-index weights, and ncm_bif, with the clean
+    band-envelope energies raised to bif_power as weights; higher is better).
+    The clean side does not depend on the exponent: bif_power is the plan's
+    default, and score_async takes another per call.  Clips of fewer than 12
+    frames and all-zero clean signals score NaN."""
+
+    _PREFIX = "cse_ncm"
+    _LABEL = "NCM"
+    _WHICH = ("ncm", "ncm_bif")
+
+    def __init__(self, clean, sr=STOI_SR, bif_power=1.0):
+        self.bif_power = _bif_power(bif_power)
+        super().__init__(clean, sr)
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True, out=None, which="both",
+                    bif_power=None):
+        """Enqueue both values of every cell; returns the [n, 2] f64 cuda result
+        (ncm, ncm_bif).  The arguments are SegSnrPlan.score_async's.
+        which="ncm" / "ncm_bif" returns that column alone, [n]; the kernel
+        computes both either way.  bif_power: the exponent of this call (default:
+        the plan's)."""
+        if which != "both" and which not in self._WHICH:
+            raise ValueError(f"which={which!r}: 'both' or one of {self._WHICH}")
+        p = self.bif_power if bif_power is None else _bif_power(bif_power)
+        off, sig, lg, n = _cell_index(self, y, y_offset, sig_of, lag)
+        dev = self.clean.device
+        if which != "both":
+            table = torch.empty((n, 2), dtype=torch.float64, device=dev)
+            self._launch(y, off, sig, lg, n, clip, (table,), p)
+            col = table[:, self._WHICH.index(which)]
+            if out is None:
+                return col.contiguous()
+            if out.shape != (n,) or out.dtype != torch.float64:
+                raise ValueError("out must be a [n] float64 tensor")
+            out.copy_(col)
+            return out
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        if out.shape != (n, 2) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [n, 2] float64 tensor")
+        self._launch(y, off, sig, lg, n, clip, (out,), p)
+        return out
+
+    def _launch(self, y, off, sig, lg, n, clip, outs, bif_power):
+        """SegSnrPlan._launch with the exponent before the output pointer; outs:
+        one contiguous [n, 2] table."""
+        step = self.cells_per_launch()
+        for s in range(0, n, step):
+            m = min(step, n - s)
+            scratch = self._scratch_for(m)
+            _lib.check(self._fn("cells")(
+                _ptr(y), _ptr(off[s:]), None if lg is None else _ptr(lg[s:]), _ptr(sig[s:]), m,
+                self.S, self.L, self.sr, 1 if clip else 0, _ptr(self.ws),
+                None if scratch is None else _ptr(scratch), bif_power, _ptr(outs[0][s:]),
+                _stream()), f"{self._PREFIX}_cells")
+
+    def score(self, y, y_offset, sig_of, lag=None, clip=True, which="both", bif_power=None):
+        """score_async, synchronised: [n, 2] numpy (or [n] for one column)."""
+        return self.score_async(y, y_offset, sig_of, lag, clip, which=which,
+                                bif_power=bif_power).cpu().numpy()
+
+
+def _bif_power(p):
+    """The band-importance exponent as a finite float >= 0, or ValueError."""
+    p = float(p)
+    if not (math.isfinite(p) and p >= 0.0):
+        raise ValueError(f"bif_power={p!r}: a finite number >= 0")
+    return p
+
+
 class SiSdrPlan:
     """Clean side of SI-SDR / SI-SIR / SI-SAR (include/cse_sisdr.h) for S
     equal-length signals (clean: [S, L] f64 cuda, any rate).  noisy ([S, L] f64
@@ -704,6 +789,48 @@ def _coherence(clean_reference, noisy_audio, enhanced_audio, sr):
         return {}
 
 
+def ncm(x, y, fs, bif_power=1.0):
+    """(ncm, ncm_bif) of y against the clean x (include/cse_ncm.h); higher is
+    better.  bif_power: the exponent of ncm_bif's band weights.  A clip of fewer
+    than 12 frames (0.12 s) and an all-zero clean signal give NaN."""
+    x, y = _pair_signals(x, y, "ncm")
+    p = _bif_power(bif_power)  # refused before anything goes to the device
+    plan = NcmPlan(torch.as_tensor(x).cuda().view(1, -1), sr=fs, bif_power=p)
+    yd = torch.as_tensor(y.astype(np.float32)).cuda()
+    return tuple(float(v) for v in plan.score(yd, [0], [0], clip=False)[0])
+
+
+def calculate_ncm(clean_reference, test_audio, sr):
+    """ncm with calculate_stoi's shape: trim to the common length, None on
+    failure (a clip of fewer than 12 frames or an all-zero clean signal
+    included)."""
+    def fn(x, y, fs):
+        v = ncm(x, y, fs)[0]
+        if math.isnan(v):
+            raise ValueError("NCM is undefined (fewer than 12 30-ms frames, or a zero clean signal)")
+        return v
+    return _calculate_quality(fn, "NCM", clean_reference, test_audio, sr)
+
+
+def _modulation(clean_reference, noisy_audio, enhanced_audio, sr):
+    """ncm_* and ncm_bif_* (noisy, enhanced) and ncm_improvement; {} on failure."""
+    try:
+        n = min(len(clean_reference), len(noisy_audio), len(enhanced_audio))
+        c = np.asarray(clean_reference)[:n]
+        v_noisy = ncm(c, np.asarray(noisy_audio)[:n], sr)
+        v_enh = ncm(c, np.asarray(enhanced_audio)[:n], sr)
+        out = {}
+        for k, name in enumerate(NcmPlan._WHICH):
+            out[f"{name}_noisy"], out[f"{name}_enhanced"] = v_noisy[k], v_enh[k]
+        out["ncm_improvement"] = v_enh[0] - v_noisy[0]
+        return out
+    except (NotImplementedError, _lib.CseError):
+        raise  # no device / unsupported: not a score failure
+    except Exception as e:  # calculate_stoi's catch-all
+        print(f"NCM calculation failed: {e}")
+        return {}
+
+
 def composite(pesq, llr, wss, segsnr):
     """(CSIG, CBAK, COVL): Hu & Loizou's (2008) composite predictions of the
     signal-distortion, background-intrusiveness and overall-quality ratings, the
@@ -849,7 +976,7 @@ def _separation(clean_reference, noisy_audio, enhanced_audio):
 
 def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, algorithm_name="",
                            quality=False, distortion=False, separation=False, wss=False,
-                           coherence=False):
+                           coherence=False, modulation=False):
     """evaluation_metrics.evaluate_audio_quality (:61-101), same keys;
     quality=True adds segsnr_* and fwsegsnr_* (noisy, enhanced, improvement);
     distortion=True adds llr_* and cep_* likewise, their improvement being
@@ -858,7 +985,9 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     wss=True adds wss_noisy, wss_enhanced and wss_improvement (noisy - enhanced);
     coherence=True adds csii_high_*, csii_mid_* and csii_low_* (noisy, enhanced)
     and i3_noisy, i3_enhanced and i3_improvement (include/cse_csii.h; a level
-    without frames gives NaN)."""
+    without frames gives NaN); modulation=True adds ncm_noisy, ncm_enhanced,
+    ncm_bif_noisy, ncm_bif_enhanced and ncm_improvement (include/cse_ncm.h, at
+    the default exponent)."""
     results = {}
     s_noisy = calculate_stoi(clean_reference, noisy_audio, sr)
     s_enh = calculate_stoi(clean_reference, enhanced_audio, sr)
@@ -889,6 +1018,8 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
                 results[f"{key}_improvement"] = v_enh - v_noisy if f.sign > 0 else v_noisy - v_enh
     if coherence:
         results.update(_coherence(clean_reference, noisy_audio, enhanced_audio, sr))
+    if modulation:
+        results.update(_modulation(clean_reference, noisy_audio, enhanced_audio, sr))
     if algorithm_name:
         print(f"\n{'=' * 60}\nEvaluation: {algorithm_name}\n{'=' * 60}")
     if "stoi_noisy" in results:
@@ -910,4 +1041,7 @@ def evaluate_audio_quality(clean_reference, noisy_audio, enhanced_audio, sr, alg
     if "i3_noisy" in results:
         print(f"I3: {results['i3_noisy']:.4f} -> {results['i3_enhanced']:.4f} (CSII mid "
               f"{results['csii_mid_noisy']:.4f} -> {results['csii_mid_enhanced']:.4f})")
+    if "ncm_noisy" in results:
+        print(f"NCM: {results['ncm_noisy']:.4f} -> {results['ncm_enhanced']:.4f} (band-importance "
+              f"form {results['ncm_bif_noisy']:.4f} -> {results['ncm_bif_enhanced']:.4f})")
     return results

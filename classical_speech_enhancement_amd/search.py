@@ -48,6 +48,14 @@ objective's.  A clip with no mid-level or no low-level frame has no I3: its
 cells hold NaN in the column and the scan skips them, like any cell without a
 score.  extended and coherence exclude each other.
 
+modulation=True (run_grid, optimize_parameters, run_sweep; stoi="modulation" in
+engine_compute) scores ncm, the normalized covariance measure with the fixed
+articulation-index weights (cse_ncm_cells, include/cse_ncm.h), in place of STOI
+in exactly the same way: the STOI column and every stoi field then hold ncm,
+and the selection and its tolerance are the STOI objective's.  A clip of fewer
+than 12 30-ms frames has no ncm (NaN, skipped).  modulation excludes extended
+and coherence: the three switches fill one column.
+
 quality=True (engine_compute, run_grid, optimize_parameters, run_sweep) adds the
 quality objective the reference takes from PESQ: segmental SNR and
 frequency-weighted segmental SNR (cse_segsnr_cells, include/cse_segsnr.h;
@@ -81,7 +89,7 @@ tables, the selection, the sweep's per-family work and the result rows loop
 over the records, and the per-family constants below (QUALITY_COLUMNS, ...) are
 derived from them.  The public signatures keep one keyword per family and pass
 the requested records, or the dict of flags, down.  STOI is no family: it owns
-column 3 of every table and the extended and coherence switches.
+column 3 of every table and the extended, coherence and modulation switches.
 
 score_noise_estimators and sweep_tracker judge noise-PSD estimates themselves,
 with no enhancement algorithm on top: the logarithmic estimation error of
@@ -361,7 +369,9 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     lag 0, lag and xstatus 0).  stoi=False leaves the STOI column NaN (no
     waveforms are kept); stoi="extended" fills it with extended STOI,
     stoi="coherence" with the CSII's I3 (include/cse_csii.h; NaN for a clip
-    without mid-level or low-level frames).
+    without mid-level or low-level frames), stoi="modulation" with the
+    normalized covariance measure ncm (include/cse_ncm.h; NaN for a clip of
+    fewer than 12 frames).
     quality=True appends segsnr and fwsegsnr (QUALITY_COLUMNS; NaN where the
     cell is not finite), scored on the side stream from the same waveforms,
     with or without STOI.  distortion=True makes the rows NCOL + 4 wide and
@@ -388,8 +398,9 @@ def engine_compute(clean, noisy, specs, ids, engine=None, align=True, stoi=True,
     and trims the cache back to
     the caller's size on return."""
     from .engine import Engine
-    if not (isinstance(stoi, bool) or stoi in ("extended", "coherence")):
-        raise ValueError(f"stoi={stoi!r}: True, False or 'extended' (or 'coherence')")
+    if not (isinstance(stoi, bool) or stoi in ("extended", "coherence", "modulation")):
+        raise ValueError(f"stoi={stoi!r}: True, False or 'extended' (or 'coherence' or "
+                         "'modulation')")
     own = engine is None
     eng = engine or Engine()
     size0 = eng.plan_cache_size
@@ -416,11 +427,34 @@ class _I3Column:
         return self.plan.score_async(y, y_offset, sig_of, lag=lag, clip=clip, which="i3")
 
 
-def _stoi_switch(extended, coherence):
-    """engine_compute's stoi= of the two switches, which exclude each other."""
-    if extended and coherence:
-        raise ValueError("extended and coherence both fill the STOI column: choose one")
-    return "extended" if extended else ("coherence" if coherence else True)
+class _NcmColumn:
+    """metrics.NcmPlan behind the one-column score_async the sweep calls: ncm."""
+
+    def __init__(self, clean):
+        from . import metrics
+        self.plan = metrics.NcmPlan(clean)
+
+    def score_async(self, y, y_offset, sig_of, lag=None, clip=True):
+        return self.plan.score_async(y, y_offset, sig_of, lag=lag, clip=clip, which="ncm")
+
+
+def _stoi_plan(kind, clean):
+    """The plan that fills the STOI column for engine_compute's stoi=kind."""
+    from . import metrics
+    if kind == "coherence":
+        return _I3Column(clean)
+    if kind == "modulation":
+        return _NcmColumn(clean)
+    return metrics.StoiPlan(clean, extended=(kind == "extended"))
+
+
+def _stoi_switch(extended, coherence, modulation=False):
+    """engine_compute's stoi= of the three switches, which exclude each other."""
+    on = [name for name, flag in (("extended", extended), ("coherence", coherence),
+                                  ("modulation", modulation)) if flag]
+    if len(on) > 1:
+        raise ValueError(f"{on[0]} and {on[1]} both fill the STOI column: choose one")
+    return on[0] if on else True
 
 
 def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, fams=()):
@@ -494,8 +528,7 @@ def _engine_compute(eng, clean, noisy, specs, ids, align, stoi, fams=()):
                                           np.asarray(clean[p], np.float64))) for p in pairs])
             # (first column, plan) in launch order: STOI, which is no family (it
             # owns column 3), then the requested families in registry order
-            plans = [(TABLE_COLUMN["stoi"], _I3Column(cl) if stoi == "coherence" else
-                      metrics.StoiPlan(cl, extended=(stoi == "extended")))] if stoi else []
+            plans = [(TABLE_COLUMN["stoi"], _stoi_plan(stoi, cl))] if stoi else []
             for f in fams:
                 cls = getattr(metrics, f.plan)
                 plans.append((f.first, cls(cl, nz) if f.plan_takes_noisy else cls(cl)))
@@ -744,7 +777,7 @@ def _select_best(specs, table, objective, tol):
 
 def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objective="snr",
              extended=False, quality=False, distortion=False, separation=False, wss=False,
-             coherence=False):
+             coherence=False, modulation=False):
     """Run every cell of ``specs`` across the ranks of ``group`` (or locally)
     and return (table [n_cells, NCOL] = sse, snr, finite, stoi, lag, xstatus;
     winners).  Every rank
@@ -752,7 +785,9 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     sequential scan, identical on every rank.  extended=True: the default
     compute (engine_compute) scores extended STOI into the stoi column; a
     compute function given by the caller scores what it scores.  coherence=True:
-    likewise with the CSII's I3 (not together with extended).  quality=True:
+    likewise with the CSII's I3 (not together with extended).  modulation=True:
+    likewise with the normalized covariance measure ncm (include/cse_ncm.h; not
+    together with extended or coherence).  quality=True:
     the table has NCOL + 2 columns (QUALITY_COLUMNS: segsnr, fwsegsnr), filled
     by the default compute; a caller's compute function returns them itself.
     distortion=True: NCOL + 4 columns (the quality columns, NaN without
@@ -762,7 +797,7 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     wss=True: NCOL + 8 columns (all of those, NaN unless asked for, then
     WSS_COLUMNS: wss), likewise."""
     import torch.distributed as dist
-    stoi_kind = _stoi_switch(extended, coherence)
+    stoi_kind = _stoi_switch(extended, coherence, modulation)
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
     rank = dist.get_rank(group) if dist_on else 0
@@ -772,7 +807,7 @@ def run_grid(clean, noisy, specs, compute=None, group=None, device=None, objecti
     flags = dict(quality=quality, distortion=distortion, separation=separation, wss=wss)
     fams = scores.requested(**flags)
     ncol = _width(fams)
-    if compute is None and (extended or coherence or fams):
+    if compute is None and (stoi_kind is not True or fams):
         def compute(clean, noisy, specs, ids):
             return engine_compute(clean, noisy, specs, ids, stoi=stoi_kind, **flags)
     compute = compute or engine_compute
@@ -907,10 +942,12 @@ def _snr_baseline(c, n):
     return math.inf if err == 0 else float(10 * np.log10(np.sum(c[:m] ** 2) / (err + 1e-10)))
 
 
-def _device_stoi(clean, test, sr, extended=False, coherence=False):
-    from .metrics import calculate_csii, calculate_stoi
+def _device_stoi(clean, test, sr, extended=False, coherence=False, modulation=False):
+    from .metrics import calculate_csii, calculate_ncm, calculate_stoi
     if coherence:
         return calculate_csii(clean, test, sr)
+    if modulation:
+        return calculate_ncm(clean, test, sr)
     return calculate_stoi(clean, test, sr, extended=extended)
 
 
@@ -933,7 +970,7 @@ def _finite(v):
 def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_ranges=None,
                         compute=None, stoi_fn=None, extended=False, quality=False,
                         quality_fn=None, distortion=False, distortion_fn=None, separation=False,
-                        separation_fn=None, coherence=False):
+                        separation_fn=None, coherence=False, modulation=False):
     """Single-pair, single-algorithm mirror of the reference's
     optimize_parameters (speech_enhancement_comparison.py:109-252), scored by
     STOI and SNR: returns {'stoi': {'score', 'params', 'cell', 'snr'},
@@ -946,6 +983,9 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     'extended': True.
     coherence=True: likewise with the CSII's I3 (include/cse_csii.h; every
     'stoi' value is then I3) and 'coherence': True; not together with extended.
+    modulation=True: likewise with the normalized covariance measure ncm
+    (include/cse_ncm.h; every 'stoi' value is then ncm) and 'modulation': True;
+    not together with extended or coherence.
     quality=True: the table has the two quality columns and the result gains
     'segsnr' and 'fwsegsnr' entries shaped like 'stoi' ({'score', 'params',
     'cell', 'snr'}, None when no cell has the score), with their baselines
@@ -969,7 +1009,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
     noisy = [np.asarray(noisy_audio, np.float64)]
     flags = dict(quality=quality, distortion=distortion, separation=separation)
     table, best = run_grid(clean, noisy, specs, compute=compute, extended=extended,
-                           coherence=coherence, **flags)
+                           coherence=coherence, modulation=modulation, **flags)
     cid, score = best[(0, alg)]
     if cid < 0:
         raise ValueError("Optimization failed for snr - no valid parameters found!")
@@ -982,11 +1022,13 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
         out["extended"] = True
     if coherence:
         out["coherence"] = True
+    if modulation:
+        out["modulation"] = True
     sid, sscore = select_best(specs, table, "stoi")[(0, alg)]
     if sid >= 0:
-        if stoi_fn is None and (extended or coherence):
+        if stoi_fn is None and (extended or coherence or modulation):
             bstoi = _device_stoi(clean[0], noisy[0], sr, extended=extended,
-                                 coherence=coherence) or 0
+                                 coherence=coherence, modulation=modulation) or 0
         else:
             bstoi = (stoi_fn or _device_stoi)(clean[0], noisy[0], sr) or 0  # :115 "or 0"
         out["stoi"] = {"score": sscore, "params": dict(specs[sid][2]), "cell": int(sid),
@@ -1032,7 +1074,7 @@ def optimize_parameters(clean_reference, noisy_audio, sr, algorithm, param_range
 
 def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=None,
               group=None, device=None, extended=False, quality=False, distortion=False,
-              separation=False, wss=False, coherence=False):
+              separation=False, wss=False, coherence=False, modulation=False):
     """The reference's batch driver (main, speech_enhancement_comparison.py:375-473)
     on the device: every pair x algorithm x grid cell scored after
     finalize_enhanced (STOI and SNR), the STOI-best and SNR-best cells per
@@ -1048,6 +1090,11 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     "stoi_coherence": True, the noisy baseline is metrics.CsiiPlan's, and the
     file names stay the same.  A pair without mid-level or low-level frames has
     no I3: its stoi fields are None.  Not together with extended.
+    modulation=True: scored and selected by the normalized covariance measure ncm
+    (include/cse_ncm.h) in the same way; the rows' stoi_* fields then hold ncm,
+    each row carries "stoi_modulation": True, the noisy baseline is
+    metrics.NcmPlan's, and the file names stay the same.  Not together with
+    extended or coherence.
     quality=True: the cells are also scored by segSNR and fwSegSNR; the
     fwSegSNR-best cell's waveform is written as ..._optimized_fwsegsnr.wav and
     each row gains segsnr_noisy, fwsegsnr_noisy, fwsegsnr_best,
@@ -1078,7 +1125,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
     flags = dict(quality=quality, distortion=distortion, separation=separation, wss=wss)
     fams = scores.requested(**flags)
     table, best = run_grid(clean, noisy, specs, group=group, device=device, extended=extended,
-                           coherence=coherence, **flags)
+                           coherence=coherence, modulation=modulation, **flags)
     rank = dist.get_rank(group) if (dist.is_available() and dist.is_initialized()) else 0
     if rank != 0:
         return None
@@ -1092,7 +1139,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
         snr_noisy = _snr_baseline(c, n)
         m = min(len(c), len(n))
         cm = torch.as_tensor(c[:m]).cuda().view(1, -1)
-        plan = _I3Column(cm) if coherence else metrics.StoiPlan(cm, extended=extended)
+        plan = _stoi_plan(_stoi_switch(extended, coherence, modulation), cm)
         nf = torch.as_tensor(n[:m].astype(np.float32)).cuda()
         stoi_noisy = _opt(float(plan.score_async(nf, [0], [0], clip=False).cpu()[0]))
         noisy_kw = {}  # per family, the unprocessed input's <name>_noisy of its baselines
@@ -1142,5 +1189,7 @@ def run_sweep(clean, noisy, stems, out_root, sr=16000, algorithms=None, grids=No
                 rows[-1]["stoi_extended"] = True
             if coherence:
                 rows[-1]["stoi_coherence"] = True
+            if modulation:
+                rows[-1]["stoi_modulation"] = True
     results.write_summary(rows, algorithms, os.path.join(out_root, "results_summary"))
     return rows
