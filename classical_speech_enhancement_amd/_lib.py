@@ -1,8 +1,8 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
-include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h, include/cse_csii.h
-and include/cse_ncm.h).
+include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h, include/cse_csii.h,
+include/cse_ncm.h and include/cse_online.h).
 
 Entry points that share a signature are declared in one loop: the noise
 trackers (TRACKER_EXPORTS) and the waveform scores on the segSNR interface
@@ -113,6 +113,27 @@ class LogErrParams(ctypes.Structure):
 
 assert ctypes.sizeof(LogErrParams) == 24
 
+
+class OnlineConfig(ctypes.Structure):
+    """cse_online_config_t (include/cse_online.h): what the online enhancer runs."""
+    _fields_ = [("n_fft", ctypes.c_int32), ("hop", ctypes.c_int32), ("algo", ctypes.c_int32),
+                ("noise_method", ctypes.c_int32), ("param", ctypes.c_float * 8),
+                ("eps", ctypes.c_double), ("mu", ctypes.c_double), ("mcra", McraParams),
+                ("spp", SppParams)]
+
+
+assert ctypes.sizeof(OnlineConfig) == 152
+
+
+class OnlineHandle(ctypes.Structure):
+    """cse_online_t (include/cse_online.h): the caller-owned host handle."""
+    _fields_ = [("cfg", OnlineConfig), ("n_streams", ctypes.c_int64), ("state", ctypes.c_void_p),
+                ("frames", ctypes.c_int64), ("primed", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(OnlineHandle) == 184
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -156,6 +177,10 @@ EXPORTS_CSII = ("cse_csii_workspace_bytes", "cse_csii_prepare", "cse_csii_scratc
 # [n_cells][2]; like CSII no record of CELL_SCORES
 EXPORTS_NCM = ("cse_ncm_workspace_bytes", "cse_ncm_prepare", "cse_ncm_scratch_bytes",
                "cse_ncm_cells")
+# include/cse_online.h (the stateful online enhancer): a host handle and one
+# device state block per batch of streams
+EXPORTS_ONLINE = ("cse_online_state_bytes", "cse_online_init", "cse_online_prime",
+                  "cse_online_push", "cse_online_finish")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -287,6 +312,14 @@ def load(path=LIB_PATH):
     lib.cse_logerr_scratch_bytes.argtypes = [i64, i32]
     lib.cse_logerr_rows.restype = i32
     lib.cse_logerr_rows.argtypes = [P, i64, i32, i32, P, P, P, P, i64, P, P, P, P, P, P, P]
+    lib.cse_online_state_bytes.restype = i64
+    lib.cse_online_state_bytes.argtypes = [i32, i64]
+    lib.cse_online_init.restype = lib.cse_online_prime.restype = i32
+    lib.cse_online_push.restype = lib.cse_online_finish.restype = i32
+    lib.cse_online_init.argtypes = [P, P, i64, P]
+    lib.cse_online_prime.argtypes = [P, P, P]
+    lib.cse_online_push.argtypes = [P, P, i32, P, P, P]
+    lib.cse_online_finish.argtypes = [P, P, P]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

@@ -53,6 +53,23 @@ __device__ CellParam gen_cell_param(const cse_cell_t* cp) {
     return prm;
 }
 
+// One bin's gain from its spectrum value y and its noise-row value nv (the PSD
+// N itself for SS, 1/max(N, eps) for the others), the n_fft-1024 row form of
+// gain_bin; returns the factor s with S = y s, as gain_bin does.
+template <int ALGO>
+__device__ __forceinline__ float gen_gain(float2& y, float nv, float& rr, float alpha_t,
+                                          const CellParam& prm, float& g) {
+    constexpr float EPS = (ALGO == CSE_ALGO_MMSE) ? 1e-12f : 1e-10f;
+    RowV rv{0.0f, 0.0f, 0.0f};
+    if (ALGO == CSE_ALGO_SS) {
+        rv.g = nv;
+    } else {
+        const float gam = fmaxf((y.x * y.x + y.y * y.y) * nv, EPS);
+        rv.g = ALGO == CSE_ALGO_OMLSA ? gam * kLog2e : gam;
+    }
+    return gain_bin<1024, ALGO>(y, rv, rr, alpha_t, prm, g);
+}
+
 // LDS layout for n_fft N (M = N/2, B = M + 1), in bytes
 struct GenLds {
     int N, M, B;
@@ -79,6 +96,110 @@ struct GenLds {
     }
 };
 
+// The window (f32, and its square in fp64) and the inverse transform's
+// twiddles; the caller's barrier follows.
+__device__ __forceinline__ void gen_tables(const GenLds& Ly, unsigned char* smem) {
+    const int N = Ly.N, M = Ly.M;
+    const int tid = threadIdx.x;
+    double* wsq = (double*)(smem + Ly.wsq);
+    float2* twm = (float2*)(smem + Ly.twm);
+    float2* twn = (float2*)(smem + Ly.twn);
+    float* win = (float*)(smem + Ly.win);
+    for (int n = tid; n < N; n += GEN_NT) {
+        const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)N);
+        win[n] = (float)w;
+        wsq[n] = w * w;
+    }
+    for (int j = tid; j < M; j += GEN_NT) {
+        double s, co;
+        sincospi(2.0 * (double)j / (double)M, &s, &co);
+        twm[j] = make_float2((float)co, (float)s);
+    }
+    for (int k = tid; k < M; k += GEN_NT) {
+        double s, co;
+        sincospi(2.0 * (double)k / (double)N, &s, &co);
+        twn[k] = make_float2((float)co, (float)s);
+    }
+}
+
+// One frame's synthesis from its spectrum S (sr, si; every thread past the
+// barrier that follows their writes): x = irfft(S), the periodic-Hann window,
+// overlap-add into the ring at the frame's first padded sample `at` (t hop).
+// Ends on a barrier.  The online enhancer (cse_online.hip) runs it per frame too.
+__device__ __forceinline__ void gen_irfft_ola(const GenLds& Ly, unsigned char* smem, int log2m,
+                                              int64_t at) {
+    const int N = Ly.N, M = Ly.M;
+    const int tid = threadIdx.x;
+    float* zr = (float*)(smem + Ly.zr);
+    float* zi = (float*)(smem + Ly.zi);
+    float* sr = (float*)(smem + Ly.sr);
+    float* si = (float*)(smem + Ly.si);
+    const float2* twm = (const float2*)(smem + Ly.twm);
+    const float2* twn = (const float2*)(smem + Ly.twn);
+    const float* win = (const float*)(smem + Ly.win);
+    float* ring = (float*)(smem + Ly.ring);
+    // ---- Z_k = E_k + i O_k into bit-reversed order for the radix-2 IFFT
+    for (int k = tid; k < M; k += GEN_NT) {
+        const float ar = sr[k], ai = si[k];
+        const float br = sr[M - k], bi = -si[M - k];  // conj S_{M-k}
+        const float er = 0.5f * (ar + br), ei = 0.5f * (ai + bi);
+        const float dr = 0.5f * (ar - br), di = 0.5f * (ai - bi);
+        const float2 w = twn[k];  // W^-k = e^{+2πi k/N}
+        const float orr = dr * w.x - di * w.y, oi = dr * w.y + di * w.x;
+        // radix 2: bit-reversed order; the direct DFT (log2m < 0): natural
+        const int r = log2m >= 0 ? (int)(__brev((unsigned)k) >> (32 - log2m)) : k;
+        zr[r] = er - oi;  // E + i O
+        zi[r] = ei + orr;
+    }
+    __syncthreads();
+    // M not a power of two (even n_fft such as 400): z[n] = sum_k Z_k
+    // e^{+2πi kn/M} directly into the S rows (consumed above)
+    float* xr = zr;
+    float* xi = zi;
+    if (log2m < 0) {
+        for (int n = tid; n < M; n += GEN_NT) {
+            float ar = 0.0f, ai = 0.0f;
+            int m = 0;  // k n mod M
+            for (int k = 0; k < M; ++k) {
+                const float2 w = twm[m];
+                ar = fmaf(zr[k], w.x, fmaf(-zi[k], w.y, ar));
+                ai = fmaf(zr[k], w.y, fmaf(zi[k], w.x, ai));
+                m += n;
+                if (m >= M) m -= M;
+            }
+            sr[n] = ar;
+            si[n] = ai;
+        }
+        __syncthreads();
+        xr = sr;
+        xi = si;
+    }
+    for (int s = 1; s <= log2m; ++s) {
+        const int half = 1 << (s - 1);
+        for (int e = tid; e < M / 2; e += GEN_NT) {
+            const int j = e & (half - 1);
+            const int i0 = ((e >> (s - 1)) << s) + j, i1 = i0 + half;
+            const float2 w = twm[j << (log2m - s)];
+            const float br = zr[i1] * w.x - zi[i1] * w.y;
+            const float bi = zr[i1] * w.y + zi[i1] * w.x;
+            const float ar = zr[i0], ai = zi[i0];
+            zr[i0] = ar + br;
+            zi[i0] = ai + bi;
+            zr[i1] = ar - br;
+            zi[i1] = ai - bi;
+        }
+        __syncthreads();
+    }
+    // ---- window, overlap-add: x[2n] = Re z[n] / M, x[2n + 1] = Im z[n] / M
+    const float inv_m = 1.0f / (float)M;
+    for (int n = tid; n < N; n += GEN_NT) {
+        const float x = ((n & 1) ? xi[n >> 1] : xr[n >> 1]) * inv_m;
+        const int ri = (int)((at + n) % N);
+        ring[ri] = fmaf(win[n], x, ring[ri]);
+    }
+    __syncthreads();
+}
+
 template <int ALGO>
 __device__ void gen_cell(const Args& a, int64_t c, int N, int log2m, unsigned char* smem) {
     const cse_cell_t* cp = a.cells + c;
@@ -92,16 +213,10 @@ __device__ void gen_cell(const Args& a, int64_t c, int N, int log2m, unsigned ch
     const int tid = threadIdx.x;
     double* wsq = (double*)(smem + Ly.wsq);
     double* red = (double*)(smem + Ly.red);
-    float* zr = (float*)(smem + Ly.zr);
-    float* zi = (float*)(smem + Ly.zi);
     float* sr = (float*)(smem + Ly.sr);
     float* si = (float*)(smem + Ly.si);
-    float2* twm = (float2*)(smem + Ly.twm);
-    float2* twn = (float2*)(smem + Ly.twn);
-    float* win = (float*)(smem + Ly.win);
     float* rr = (float*)(smem + Ly.rr);
     float* ring = (float*)(smem + Ly.ring);
-    constexpr float EPS = (ALGO == CSE_ALGO_MMSE) ? 1e-12f : 1e-10f;
 
     const int64_t len = a.len;
     const int T = (int)(1 + len / hop);
@@ -115,22 +230,8 @@ __device__ void gen_cell(const Args& a, int64_t c, int N, int log2m, unsigned ch
     const int64_t out_len = a.out_len;
     const CellParam prm = gen_cell_param<ALGO>(cp);
 
-    for (int n = tid; n < N; n += GEN_NT) {
-        const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)N);
-        win[n] = (float)w;
-        wsq[n] = w * w;
-        ring[n] = 0.0f;
-    }
-    for (int j = tid; j < M; j += GEN_NT) {
-        double s, co;
-        sincospi(2.0 * (double)j / (double)M, &s, &co);
-        twm[j] = make_float2((float)co, (float)s);
-    }
-    for (int k = tid; k < M; k += GEN_NT) {
-        double s, co;
-        sincospi(2.0 * (double)k / (double)N, &s, &co);
-        twn[k] = make_float2((float)co, (float)s);
-    }
+    gen_tables(Ly, smem);
+    for (int n = tid; n < N; n += GEN_NT) ring[n] = 0.0f;
     for (int k = tid; k < B; k += GEN_NT) rr[k] = 0.0f;
     __syncthreads();
 
@@ -173,15 +274,8 @@ __device__ void gen_cell(const Args& a, int64_t c, int N, int log2m, unsigned ch
         for (int k = tid; k < B; k += GEN_NT) {
             float2 y = Yb[(int64_t)t * B + k];
             const float nv = Nb[t * nstride + k];
-            RowV rv{0.0f, 0.0f, 0.0f};
-            if (ALGO == CSE_ALGO_SS) {
-                rv.g = nv;
-            } else {
-                const float gam = fmaxf((y.x * y.x + y.y * y.y) * nv, EPS);
-                rv.g = ALGO == CSE_ALGO_OMLSA ? gam * kLog2e : gam;
-            }
             float st = rr[k], g;
-            const float s = gain_bin<1024, ALGO>(y, rv, st, alpha_t, prm, g);
+            const float s = gen_gain<ALGO>(y, nv, st, alpha_t, prm, g);
             rr[k] = st;
             if (gout) gout[(int64_t)t * B + k] = g;
             float re = y.x * s, im = y.y * s;
@@ -190,66 +284,7 @@ __device__ void gen_cell(const Args& a, int64_t c, int N, int log2m, unsigned ch
             si[k] = im;
         }
         __syncthreads();
-        // ---- Z_k = E_k + i O_k into bit-reversed order for the radix-2 IFFT
-        for (int k = tid; k < M; k += GEN_NT) {
-            const float ar = sr[k], ai = si[k];
-            const float br = sr[M - k], bi = -si[M - k];  // conj S_{M-k}
-            const float er = 0.5f * (ar + br), ei = 0.5f * (ai + bi);
-            const float dr = 0.5f * (ar - br), di = 0.5f * (ai - bi);
-            const float2 w = twn[k];  // W^-k = e^{+2πi k/N}
-            const float orr = dr * w.x - di * w.y, oi = dr * w.y + di * w.x;
-            // radix 2: bit-reversed order; the direct DFT (log2m < 0): natural
-            const int r = log2m >= 0 ? (int)(__brev((unsigned)k) >> (32 - log2m)) : k;
-            zr[r] = er - oi;  // E + i O
-            zi[r] = ei + orr;
-        }
-        __syncthreads();
-        // M not a power of two (even n_fft such as 400): z[n] = sum_k Z_k
-        // e^{+2πi kn/M} directly into the S rows (consumed above)
-        float* xr = zr;
-        float* xi = zi;
-        if (log2m < 0) {
-            for (int n = tid; n < M; n += GEN_NT) {
-                float ar = 0.0f, ai = 0.0f;
-                int m = 0;  // k n mod M
-                for (int k = 0; k < M; ++k) {
-                    const float2 w = twm[m];
-                    ar = fmaf(zr[k], w.x, fmaf(-zi[k], w.y, ar));
-                    ai = fmaf(zr[k], w.y, fmaf(zi[k], w.x, ai));
-                    m += n;
-                    if (m >= M) m -= M;
-                }
-                sr[n] = ar;
-                si[n] = ai;
-            }
-            __syncthreads();
-            xr = sr;
-            xi = si;
-        }
-        for (int s = 1; s <= log2m; ++s) {
-            const int half = 1 << (s - 1);
-            for (int e = tid; e < M / 2; e += GEN_NT) {
-                const int j = e & (half - 1);
-                const int i0 = ((e >> (s - 1)) << s) + j, i1 = i0 + half;
-                const float2 w = twm[j << (log2m - s)];
-                const float br = zr[i1] * w.x - zi[i1] * w.y;
-                const float bi = zr[i1] * w.y + zi[i1] * w.x;
-                const float ar = zr[i0], ai = zi[i0];
-                zr[i0] = ar + br;
-                zi[i0] = ai + bi;
-                zr[i1] = ar - br;
-                zi[i1] = ai - bi;
-            }
-            __syncthreads();
-        }
-        // ---- window, overlap-add: x[2n] = Re z[n] / M, x[2n + 1] = Im z[n] / M
-        const float inv_m = 1.0f / (float)M;
-        for (int n = tid; n < N; n += GEN_NT) {
-            const float x = ((n & 1) ? xi[n >> 1] : xr[n >> 1]) * inv_m;
-            const int ri = (int)(((int64_t)t * hop + n) % N);
-            ring[ri] = fmaf(win[n], x, ring[ri]);
-        }
-        __syncthreads();
+        gen_irfft_ola(Ly, smem, log2m, (int64_t)t * hop);
         // ---- positions [t hop - N/2, (t + 1) hop - N/2) are final
         const int64_t p0 = (int64_t)t * hop - N / 2;
         retire(p0, p0 + hop, (int64_t)t * hop + N / 2);
@@ -274,6 +309,8 @@ __device__ void gen_cell(const Args& a, int64_t c, int N, int log2m, unsigned ch
     }
 }
 
+// (CSE_GENERIC_DEVICE_ONLY: the device functions above only, for cse_online.hip)
+#ifndef CSE_GENERIC_DEVICE_ONLY
 __global__ void __launch_bounds__(GEN_NT) enhance_generic_kernel(Args a, int N, int log2m) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int64_t c = blockIdx.x;
@@ -288,8 +325,11 @@ __global__ void __launch_bounds__(GEN_NT) enhance_generic_kernel(Args a, int N, 
     }
 }
 
+#endif  // !CSE_GENERIC_DEVICE_ONLY
+
 }  // namespace cse
 
+#ifndef CSE_GENERIC_DEVICE_ONLY
 using namespace cse;
 
 extern "C" int cse_enhance_cells_generic(int n_fft, int64_t len, const cse_cell_t* cells,
@@ -332,3 +372,4 @@ extern "C" int cse_enhance_cells_generic(int n_fft, int64_t len, const cse_cell_
     CSE_CHECK_LAUNCH(name);
     return CSE_OK;
 }
+#endif  // !CSE_GENERIC_DEVICE_ONLY

@@ -67,6 +67,32 @@ __device__ __forceinline__ void mcra_track(McraState& s, const McraK& k, double 
     s.lam = ad * s.lam + (1.0 - ad) * pc;
 }
 
+// the parameter checks of cse_noise_mcra, under the caller's name (the online
+// enhancer, cse_online.hip, includes this file with CSE_MCRA_DEVICE_ONLY)
+static int mcra_check_params(const char* name, const cse_mcra_params_t* prm) {
+    const double al[3] = {prm->alpha_s, prm->alpha_d, prm->alpha_p};
+    for (int i = 0; i < 3; ++i)  // written so that NaN fails
+        CSE_CHECK_ARG(al[i] >= 0.0 && al[i] < 1.0,
+                      "%s: alpha_s=%g alpha_d=%g alpha_p=%g not all in [0, 1)", name, al[0], al[1],
+                      al[2]);
+    CSE_CHECK_ARG(prm->delta > 0.0, "%s: delta=%g not > 0", name, prm->delta);
+    CSE_CHECK_ARG(prm->window_frames >= 2, "%s: window_frames=%d < 2", name, prm->window_frames);
+    return CSE_OK;
+}
+
+static McraK mcra_constants(const cse_mcra_params_t* prm) {
+    McraK k;
+    k.a_s = prm->alpha_s;
+    k.c_s = 1.0 - prm->alpha_s;
+    k.a_d = prm->alpha_d;
+    k.c_d = 1.0 - prm->alpha_d;
+    k.a_p = prm->alpha_p;
+    k.c_p = 1.0 - prm->alpha_p;
+    k.delta = prm->delta;
+    return k;
+}
+
+#ifndef CSE_MCRA_DEVICE_ONLY
 __global__ void __launch_bounds__(64) mcra_kernel(const double* __restrict__ P, int T, int B,
                                                   int nblk, McraK k, int L, double eps,
                                                   float* __restrict__ N) {
@@ -138,8 +164,11 @@ __global__ void __launch_bounds__(64) mcra_kernel(const double* __restrict__ P, 
     }
 }
 
+#endif  // !CSE_MCRA_DEVICE_ONLY
+
 }  // namespace cse
 
+#ifndef CSE_MCRA_DEVICE_ONLY
 using namespace cse;
 
 extern "C" void cse_mcra_default_params(cse_mcra_params_t* prm) {
@@ -160,28 +189,15 @@ extern "C" int cse_noise_mcra(const double* P, int64_t n_sig, int T, int B,
     CSE_CHECK_ARG(n_sig >= 0 && T >= 1 && B >= 33 && B <= 2049,
                   "cse_noise_mcra: bad shape n_sig=%lld T=%d B=%d (B in [33, 2049])",
                   (long long)n_sig, T, B);
-    const double al[3] = {prm->alpha_s, prm->alpha_d, prm->alpha_p};
-    for (int i = 0; i < 3; ++i)  // written so that NaN fails
-        CSE_CHECK_ARG(al[i] >= 0.0 && al[i] < 1.0,
-                      "cse_noise_mcra: alpha_s=%g alpha_d=%g alpha_p=%g not all in [0, 1)", al[0],
-                      al[1], al[2]);
-    CSE_CHECK_ARG(prm->delta > 0.0, "cse_noise_mcra: delta=%g not > 0", prm->delta);
-    CSE_CHECK_ARG(prm->window_frames >= 2, "cse_noise_mcra: window_frames=%d < 2",
-                  prm->window_frames);
+    if (mcra_check_params("cse_noise_mcra", prm) != CSE_OK) return CSE_EINVAL;
     const int nblk = ceil_div(B, 64);
     CSE_CHECK_ARG(n_sig * nblk <= 0x7fffffffLL, "cse_noise_mcra: n_sig=%lld too many for one launch",
                   (long long)n_sig);
     if (n_sig == 0) return CSE_OK;
-    McraK k;
-    k.a_s = prm->alpha_s;
-    k.c_s = 1.0 - prm->alpha_s;
-    k.a_d = prm->alpha_d;
-    k.c_d = 1.0 - prm->alpha_d;
-    k.a_p = prm->alpha_p;
-    k.c_p = 1.0 - prm->alpha_p;
-    k.delta = prm->delta;
+    const McraK k = mcra_constants(prm);
     hipLaunchKernelGGL(mcra_kernel, dim3((unsigned)(n_sig * nblk)), dim3(64), 0,
                        (hipStream_t)stream, P, T, B, nblk, k, (int)prm->window_frames, eps, N);
     CSE_CHECK_LAUNCH("cse_noise_mcra");
     return CSE_OK;
 }
+#endif  // !CSE_MCRA_DEVICE_ONLY

@@ -50,6 +50,42 @@ __device__ __forceinline__ double spp_frame(double& lam, double& pm, const SppK&
     return lam;
 }
 
+// the parameter checks of cse_noise_spp, under the caller's name (the online
+// enhancer, cse_online.hip, includes this file with CSE_SPP_DEVICE_ONLY)
+static int spp_check_params(const char* name, const cse_spp_params_t* prm) {
+    // every range written so that NaN fails
+    CSE_CHECK_ARG(prm->prior_h1 > 0.0 && prm->prior_h1 < 1.0 && prm->ph_max > 0.0 &&
+                      prm->ph_max < 1.0,
+                  "%s: prior_h1=%g ph_max=%g not both in (0, 1)", name, prm->prior_h1,
+                  prm->ph_max);
+    CSE_CHECK_ARG(prm->alpha_pow >= 0.0 && prm->alpha_pow < 1.0 && prm->alpha_ph >= 0.0 &&
+                      prm->alpha_ph < 1.0,
+                  "%s: alpha_pow=%g alpha_ph=%g not both in [0, 1)", name, prm->alpha_pow,
+                  prm->alpha_ph);
+    CSE_CHECK_ARG(isfinite(prm->xi_opt_db), "%s: xi_opt_db=%g not finite", name, prm->xi_opt_db);
+    CSE_CHECK_ARG(prm->init_frames >= 1, "%s: init_frames=%d < 1", name, prm->init_frames);
+    return CSE_OK;
+}
+
+// the header's host-side constants
+static SppK spp_constants(const cse_spp_params_t* prm) {
+    // the base through a volatile: pow stays the library's pow (no exp10 in its place)
+    volatile double ten = 10.0;
+    const double xi = pow(ten, prm->xi_opt_db / 10.0);
+    SppK k;
+    k.prior = prm->prior_h1 / (1.0 - prm->prior_h1);
+    k.c0 = log(1.0 / (1.0 + xi));
+    k.c1 = xi / (1.0 + xi);
+    k.a_ph = prm->alpha_ph;
+    k.c_ph = 1.0 - prm->alpha_ph;
+    k.ph_max = prm->ph_max;
+    k.a_pow = prm->alpha_pow;
+    k.c_pow = 1.0 - prm->alpha_pow;
+    k.prior_h1 = prm->prior_h1;
+    return k;
+}
+
+#ifndef CSE_SPP_DEVICE_ONLY
 __global__ void __launch_bounds__(64) spp_kernel(const double* __restrict__ P, int T, int B,
                                                  int nblk, SppK k, int K, double eps,
                                                  float* __restrict__ N) {
@@ -87,8 +123,11 @@ __global__ void __launch_bounds__(64) spp_kernel(const double* __restrict__ P, i
         Ns[(int64_t)t * B] = (float)fmax(spp_frame(lam, pm, k, Ps[(int64_t)t * B]), eps);
 }
 
+#endif  // !CSE_SPP_DEVICE_ONLY
+
 }  // namespace cse
 
+#ifndef CSE_SPP_DEVICE_ONLY
 using namespace cse;
 
 extern "C" void cse_spp_default_params(cse_spp_params_t* prm) {
@@ -110,38 +149,16 @@ extern "C" int cse_noise_spp(const double* P, int64_t n_sig, int T, int B,
     CSE_CHECK_ARG(n_sig >= 0 && T >= 1 && B >= 33 && B <= 2049,
                   "cse_noise_spp: bad shape n_sig=%lld T=%d B=%d (B in [33, 2049])",
                   (long long)n_sig, T, B);
-    // every range written so that NaN fails
-    CSE_CHECK_ARG(prm->prior_h1 > 0.0 && prm->prior_h1 < 1.0 && prm->ph_max > 0.0 &&
-                      prm->ph_max < 1.0,
-                  "cse_noise_spp: prior_h1=%g ph_max=%g not both in (0, 1)", prm->prior_h1,
-                  prm->ph_max);
-    CSE_CHECK_ARG(prm->alpha_pow >= 0.0 && prm->alpha_pow < 1.0 && prm->alpha_ph >= 0.0 &&
-                      prm->alpha_ph < 1.0,
-                  "cse_noise_spp: alpha_pow=%g alpha_ph=%g not both in [0, 1)", prm->alpha_pow,
-                  prm->alpha_ph);
-    CSE_CHECK_ARG(isfinite(prm->xi_opt_db), "cse_noise_spp: xi_opt_db=%g not finite",
-                  prm->xi_opt_db);
-    CSE_CHECK_ARG(prm->init_frames >= 1, "cse_noise_spp: init_frames=%d < 1", prm->init_frames);
+    if (spp_check_params("cse_noise_spp", prm) != CSE_OK) return CSE_EINVAL;
     const int nblk = ceil_div(B, 64);
     CSE_CHECK_ARG(n_sig * nblk <= 0x7fffffffLL, "cse_noise_spp: n_sig=%lld too many for one launch",
                   (long long)n_sig);
     if (n_sig == 0) return CSE_OK;
-    // the base through a volatile: pow stays the library's pow (no exp10 in its place)
-    volatile double ten = 10.0;
-    const double xi = pow(ten, prm->xi_opt_db / 10.0);
-    SppK k;
-    k.prior = prm->prior_h1 / (1.0 - prm->prior_h1);
-    k.c0 = log(1.0 / (1.0 + xi));
-    k.c1 = xi / (1.0 + xi);
-    k.a_ph = prm->alpha_ph;
-    k.c_ph = 1.0 - prm->alpha_ph;
-    k.ph_max = prm->ph_max;
-    k.a_pow = prm->alpha_pow;
-    k.c_pow = 1.0 - prm->alpha_pow;
-    k.prior_h1 = prm->prior_h1;
+    const SppK k = spp_constants(prm);
     const int K = prm->init_frames < T ? prm->init_frames : T;
     hipLaunchKernelGGL(spp_kernel, dim3((unsigned)(n_sig * nblk)), dim3(64), 0,
                        (hipStream_t)stream, P, T, B, nblk, k, K, eps, N);
     CSE_CHECK_LAUNCH("cse_noise_spp");
     return CSE_OK;
 }
+#endif  // !CSE_SPP_DEVICE_ONLY
