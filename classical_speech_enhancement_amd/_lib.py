@@ -2,7 +2,7 @@
 include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
 include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h, include/cse_csii.h,
-include/cse_ncm.h and include/cse_online.h).
+include/cse_ncm.h, include/cse_online.h and include/cse_online_pool.h).
 
 Entry points that share a signature are declared in one loop: the noise
 trackers (TRACKER_EXPORTS) and the waveform scores on the segSNR interface
@@ -134,6 +134,41 @@ class OnlineHandle(ctypes.Structure):
 
 assert ctypes.sizeof(OnlineHandle) == 184
 
+
+class PoolParams(ctypes.Structure):
+    """cse_pool_params_t (include/cse_online_pool.h): one slot's parameter values."""
+    _fields_ = [("param", ctypes.c_float * 8), ("mu", ctypes.c_double), ("mcra", McraParams),
+                ("spp", SppParams)]
+
+
+assert ctypes.sizeof(PoolParams) == 128
+
+
+class PoolItem(ctypes.Structure):
+    """cse_pool_item_t: one entry of a step's list."""
+    _fields_ = [("slot", ctypes.c_int32), ("k", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(PoolItem) == 8
+
+
+class PoolSlot(ctypes.Structure):
+    """cse_pool_slot_t: the library's host bookkeeping of one slot."""
+    _fields_ = [("frames", ctypes.c_int64), ("open", ctypes.c_int32),
+                ("first_frames", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(PoolSlot) == 16
+
+
+class PoolHandle(ctypes.Structure):
+    """cse_pool_t: the caller-owned host handle of a pool."""
+    _fields_ = [("cfg", OnlineConfig), ("capacity", ctypes.c_int64), ("state", ctypes.c_void_p),
+                ("work", ctypes.c_void_p), ("slots", ctypes.POINTER(PoolSlot))]
+
+
+assert ctypes.sizeof(PoolHandle) == 184
+
 EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_noise_workspace_bytes", "cse_noise_default_params", "cse_noise_estimate_ex",
            "cse_noise_estimate", "cse_noise_smooth", "cse_noise_median",
@@ -181,6 +216,11 @@ EXPORTS_NCM = ("cse_ncm_workspace_bytes", "cse_ncm_prepare", "cse_ncm_scratch_by
 # device state block per batch of streams
 EXPORTS_ONLINE = ("cse_online_state_bytes", "cse_online_init", "cse_online_prime",
                   "cse_online_push", "cse_online_finish")
+# include/cse_online_pool.h (a pool of online streams with slots that open, step
+# and close one by one): a host handle, a host slot table, a device state block
+# and a device work list per pool
+EXPORTS_POOL = ("cse_pool_state_bytes", "cse_pool_work_bytes", "cse_pool_init", "cse_pool_open",
+                "cse_pool_step", "cse_pool_close", "cse_pool_drop")
 XCORR_OK, XCORR_FLAT, XCORR_NONFINITE = 0, 1, 2  # FLAT: slow exact path ran (lag exact)
 
 
@@ -320,6 +360,16 @@ def load(path=LIB_PATH):
     lib.cse_online_prime.argtypes = [P, P, P]
     lib.cse_online_push.argtypes = [P, P, i32, P, P, P]
     lib.cse_online_finish.argtypes = [P, P, P]
+    lib.cse_pool_state_bytes.restype = lib.cse_pool_work_bytes.restype = i64
+    lib.cse_pool_state_bytes.argtypes = [i32, i64]
+    lib.cse_pool_work_bytes.argtypes = [i64]
+    for entry in EXPORTS_POOL[2:]:
+        getattr(lib, entry).restype = i32
+    lib.cse_pool_init.argtypes = [P, P, i64, P, P, P]   # handle, config, capacity, state, work, slots
+    lib.cse_pool_open.argtypes = [P, i64, P, P, P]      # handle, slot, params or NULL, x_head, stream
+    lib.cse_pool_step.argtypes = [P, P, i32, P, P, P, P]  # handle, items, n, x, y, n_out, stream
+    lib.cse_pool_close.argtypes = [P, i64, P, P]        # handle, slot, y_tail, stream
+    lib.cse_pool_drop.argtypes = [P, i64]
     lib.cse_enhance_cells.restype = i32
     lib.cse_enhance_cells.argtypes = [i32, i64, P, i64, P, P, P, P, i64, P, P, P, P]
     lib.cse_enhance_cells_short_hop.restype = i32

@@ -15,7 +15,10 @@
 //   tracker    the per-bin device functions of cse_mcra.hip / cse_spp.hip
 //   gain       gen_gain (cse_enhance_generic.hip): gain_bin<1024, ALGO>
 //   synthesis  gen_irfft_ola (cse_enhance_generic.hip)
-// are included, not restated.
+// are included, not restated.  The frames, the prime and the finish of one
+// stream are device functions (on_frames, on_prime, on_finish) that the pool of
+// cse_online_pool.hip runs on its slots as the kernels here run them on the
+// streams of a batch.
 #define CSE_ENHANCE_DEVICE_ONLY 1
 #define CSE_GENERIC_DEVICE_ONLY 1
 #define CSE_MCRA_DEVICE_ONLY 1
@@ -133,24 +136,24 @@ __device__ __forceinline__ void on_analysis(const OnArgs& a, const OnLds& Lo, un
     __syncthreads();
 }
 
+// The frames [a.t0, a.t0 + a.k) of one stream, by one workgroup: sb is the
+// stream's state block, xs / ys its k hop samples in and out, ns its [k][B]
+// rows or null.  Of `a` it reads N, log2n, hop, k, t0 and the parameters, not
+// state, x, y or n_out: the lockstep kernel and the pool's (cse_online_pool.hip)
+// find a stream's pointers in their own ways.
 template <int ALGO, int METHOD>
-__global__ void __launch_bounds__(GEN_NT) online_push_kernel(OnArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+__device__ __forceinline__ void on_frames(const OnArgs& a, unsigned char* smem, unsigned char* sb,
+                                          const double* xs, float* ys, float* ns) {
     const int N = a.N, M = N / 2, B = M + 1, hop = a.hop, k = a.k;
     const int tid = threadIdx.x;
-    const int64_t sig = blockIdx.x;
     const GenLds Ly(N);
     const OnLds Lo(N);
     const OnState Os(N);
-    unsigned char* sb = a.state + sig * Os.total;
     double* tail = (double*)(sb + Os.tail);
     double* trk = (double*)(sb + Os.trk);
     double* smu = (double*)(sb + Os.mu);
     float* rr_g = (float*)(sb + Os.rr);
     float* ring_g = (float*)(sb + Os.ring);
-    const double* xs = a.x + sig * (int64_t)k * hop;
-    float* ys = a.y + sig * (int64_t)k * hop;
-    float* ns = a.n_out ? a.n_out + sig * (int64_t)k * B : nullptr;
 
     const double* wsq = (const double*)(smem + Ly.wsq);
     float* sr = (float*)(smem + Ly.sr);
@@ -287,33 +290,50 @@ __global__ void __launch_bounds__(GEN_NT) online_push_kernel(OnArgs a) {
     }
 }
 
-// all state zero, then the input tail
-__global__ void __launch_bounds__(GEN_NT) online_prime_kernel(unsigned char* state, int N, int hop,
-                                                              const double* x_head) {
+// (CSE_ONLINE_DEVICE_ONLY: the device functions and host checks only, no
+// kernel and no entry point, for cse_online_pool.hip)
+#ifndef CSE_ONLINE_DEVICE_ONLY
+template <int ALGO, int METHOD>
+__global__ void __launch_bounds__(GEN_NT) online_push_kernel(OnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int64_t sig = blockIdx.x;
+    const int64_t B = a.N / 2 + 1;
+    on_frames<ALGO, METHOD>(a, smem, a.state + sig * OnState(a.N).total,
+                            a.x + sig * (int64_t)a.k * a.hop, a.y + sig * (int64_t)a.k * a.hop,
+                            a.n_out ? a.n_out + sig * (int64_t)a.k * B : nullptr);
+}
+#endif  // !CSE_ONLINE_DEVICE_ONLY
+
+// one stream's block sb: all state zero, then the input tail xh [N - hop]
+__device__ __forceinline__ void on_prime(unsigned char* sb, int N, int hop, const double* xh) {
     const OnState Os(N);
-    unsigned char* sb = state + (int64_t)blockIdx.x * Os.total;
     uint32_t* w = (uint32_t*)sb;
     const int nt = N - hop;
     // the words past the tail, then the tail (disjoint: no barrier)
     for (int64_t i = Os.trk / 4 + threadIdx.x; i < Os.total / 4; i += GEN_NT) w[i] = 0u;
     double* tail = (double*)(sb + Os.tail);
-    const double* xh = x_head + (int64_t)blockIdx.x * nt;
     for (int i = threadIdx.x; i < N; i += GEN_NT) tail[i] = i < nt ? xh[i] : 0.0;
 }
 
-// the ring's last n_fft - hop samples: padded [T hop, (T - 1) hop + n_fft)
-__global__ void __launch_bounds__(GEN_NT) online_finish_kernel(const unsigned char* state, int N,
-                                                               int hop, int64_t T, float* y_tail) {
-    __shared__ double wsq[2048];
-    const OnState Os(N);
-    const float* ring = (const float*)(state + (int64_t)blockIdx.x * Os.total + Os.ring);
+#ifndef CSE_ONLINE_DEVICE_ONLY
+__global__ void __launch_bounds__(GEN_NT) online_prime_kernel(unsigned char* state, int N, int hop,
+                                                              const double* x_head) {
+    on_prime(state + (int64_t)blockIdx.x * OnState(N).total, N, hop,
+             x_head + (int64_t)blockIdx.x * (N - hop));
+}
+#endif  // !CSE_ONLINE_DEVICE_ONLY
+
+// the last n_fft - hop samples of one stream's ring (block sb, T frames run):
+// padded [T hop, (T - 1) hop + n_fft) -> out [N - hop]; wsq: LDS, f64 [N]
+__device__ __forceinline__ void on_finish(const unsigned char* sb, int N, int hop, int64_t T,
+                                          float* out, double* wsq) {
+    const float* ring = (const float*)(sb + OnState(N).ring);
     for (int n = threadIdx.x; n < N; n += GEN_NT) {
         const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)N);
         wsq[n] = w * w;
     }
     __syncthreads();
     const int nt = N - hop;
-    float* out = y_tail + (int64_t)blockIdx.x * nt;
     for (int i = threadIdx.x; i < nt; i += GEN_NT) {
         const int64_t q = T * hop + i;
         const float v = ring[q % N];
@@ -324,32 +344,22 @@ __global__ void __launch_bounds__(GEN_NT) online_finish_kernel(const unsigned ch
     }
 }
 
-template <int ALGO>
-static const void* push_fn(int method) {
-    return method == CSE_NOISE_MCRA ? (const void*)online_push_kernel<ALGO, CSE_NOISE_MCRA>
-                                    : (const void*)online_push_kernel<ALGO, CSE_NOISE_SPP>;
+#ifndef CSE_ONLINE_DEVICE_ONLY
+__global__ void __launch_bounds__(GEN_NT) online_finish_kernel(const unsigned char* state, int N,
+                                                               int hop, int64_t T, float* y_tail) {
+    __shared__ double wsq[2048];
+    on_finish(state + (int64_t)blockIdx.x * OnState(N).total, N, hop, T,
+              y_tail + (int64_t)blockIdx.x * (N - hop), wsq);
 }
+#endif  // !CSE_ONLINE_DEVICE_ONLY
 
 static bool online_shape_ok(int n_fft) {
     return n_fft >= 128 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0;
 }
 
-}  // namespace cse
-
-using namespace cse;
-
-extern "C" int64_t cse_online_state_bytes(int n_fft, int64_t n_streams) {
-    if (!online_shape_ok(n_fft) || n_streams < 0) return -1;
-    return OnState(n_fft).total * n_streams;
-}
-
-extern "C" int cse_online_init(cse_online_t* h, const cse_online_config_t* cfg, int64_t n_streams,
-                               void* state) {
-    const char* name = "cse_online_init";
-    CSE_CHECK_ARG(h && cfg, "%s: NULL handle or configuration", name);
-    CSE_CHECK_ARG(n_streams >= 0 && n_streams < (1ll << 31), "%s: n_streams=%lld", name,
-                  (long long)n_streams);
-    CSE_CHECK_ARG(state || n_streams == 0, "%s: NULL state", name);
+// the configuration checks of cse_online_init, under the caller's name (the
+// pool, cse_online_pool.hip, includes this file with CSE_ONLINE_DEVICE_ONLY)
+static int online_check_config(const char* name, const cse_online_config_t* cfg) {
     CSE_CHECK_ARG(online_shape_ok(cfg->n_fft), "%s: n_fft=%d (a power of two in [128, 2048])", name,
                   cfg->n_fft);
     CSE_CHECK_ARG(cfg->hop == cfg->n_fft / 8 || cfg->hop == cfg->n_fft / 4 ||
@@ -381,6 +391,56 @@ extern "C" int cse_online_init(cse_online_t* h, const cse_online_config_t* cfg, 
     }
     CSE_CHECK_ARG(cfg->eps > 0.0, "%s: eps=%g not > 0", name, cfg->eps);
     CSE_CHECK_ARG(cfg->mu == cfg->mu, "%s: mu is NaN", name);
+    return CSE_OK;
+}
+
+// the arguments a frame reads besides the launch's own (k, t0, the pointers)
+static void online_fill_args(OnArgs& a, int n_fft, int hop, int algo, int noise_method,
+                             const float* param, const cse_mcra_params_t* mcra,
+                             const cse_spp_params_t* spp, double eps, double mu) {
+    a.N = n_fft;
+    a.log2n = __builtin_ctz((unsigned)n_fft);
+    a.hop = hop;
+    a.cell = cse_cell_t{};
+    a.cell.algo = algo;
+    a.cell.hop = hop;
+    for (int i = 0; i < 8; ++i) a.cell.param[i] = param[i];
+    a.mk = mcra_constants(mcra);
+    a.sk = noise_method == CSE_NOISE_SPP ? spp_constants(spp) : SppK{};
+    a.L = mcra->window_frames;
+    a.K = spp->init_frames;
+    a.eps = eps;
+    a.mu = mu;
+    a.inv_eps = (float)eps;
+}
+
+#ifndef CSE_ONLINE_DEVICE_ONLY
+template <int ALGO>
+static const void* push_fn(int method) {
+    return method == CSE_NOISE_MCRA ? (const void*)online_push_kernel<ALGO, CSE_NOISE_MCRA>
+                                    : (const void*)online_push_kernel<ALGO, CSE_NOISE_SPP>;
+}
+#endif  // !CSE_ONLINE_DEVICE_ONLY
+
+}  // namespace cse
+
+#ifndef CSE_ONLINE_DEVICE_ONLY
+
+using namespace cse;
+
+extern "C" int64_t cse_online_state_bytes(int n_fft, int64_t n_streams) {
+    if (!online_shape_ok(n_fft) || n_streams < 0) return -1;
+    return OnState(n_fft).total * n_streams;
+}
+
+extern "C" int cse_online_init(cse_online_t* h, const cse_online_config_t* cfg, int64_t n_streams,
+                               void* state) {
+    const char* name = "cse_online_init";
+    CSE_CHECK_ARG(h && cfg, "%s: NULL handle or configuration", name);
+    CSE_CHECK_ARG(n_streams >= 0 && n_streams < (1ll << 31), "%s: n_streams=%lld", name,
+                  (long long)n_streams);
+    CSE_CHECK_ARG(state || n_streams == 0, "%s: NULL state", name);
+    if (online_check_config(name, cfg) != CSE_OK) return CSE_EINVAL;
     h->cfg = *cfg;
     h->cfg.mu = fmin(fmax(cfg->mu, 0.0), 0.9999);
     h->n_streams = n_streams;
@@ -419,26 +479,14 @@ extern "C" int cse_online_push(cse_online_t* h, const double* x, int k, float* y
     CSE_CHECK_ARG((int64_t)k * c.hop < (1ll << 30) && h->frames + k < (1ll << 40),
                   "%s: k=%d too many frames", name, k);
     OnArgs a;
-    a.N = c.n_fft;
-    a.log2n = __builtin_ctz((unsigned)c.n_fft);
-    a.hop = c.hop;
+    online_fill_args(a, c.n_fft, c.hop, c.algo, c.noise_method, c.param, &c.mcra, &c.spp, c.eps,
+                     c.mu);
     a.k = k;
     a.t0 = h->frames;
     a.state = (unsigned char*)h->state;
     a.x = x;
     a.y = y;
     a.n_out = n_out;
-    a.cell = cse_cell_t{};
-    a.cell.algo = c.algo;
-    a.cell.hop = c.hop;
-    for (int i = 0; i < 8; ++i) a.cell.param[i] = c.param[i];
-    a.mk = mcra_constants(&c.mcra);
-    a.sk = c.noise_method == CSE_NOISE_SPP ? spp_constants(&c.spp) : SppK{};
-    a.L = c.mcra.window_frames;
-    a.K = c.spp.init_frames;
-    a.eps = c.eps;
-    a.mu = c.mu;
-    a.inv_eps = (float)c.eps;
     const void* fn = nullptr;
     switch (c.algo) {
         case CSE_ALGO_SS: fn = push_fn<CSE_ALGO_SS>(c.noise_method); break;
@@ -475,3 +523,4 @@ extern "C" int cse_online_finish(cse_online_t* h, float* y_tail, cse_stream_t st
     CSE_CHECK_LAUNCH(name);
     return CSE_OK;
 }
+#endif  // !CSE_ONLINE_DEVICE_ONLY

@@ -9,12 +9,21 @@ side of it:
                   carries; host-only, raises for what the online path refuses
   DeviceCore      the device calls (cse_online_init / prime / push / finish) on
                   torch buffers; no CPU fallback
-  OnlineEnhancer  buffers input to whole hops, builds the reflect padding at
-                  both ends, holds back spp's first init_frames frames, and
-                  trims the emitted padded samples to the caller's positions
+  StreamHost      one stream's (or one lockstep batch's) host logic: buffers
+                  input to whole hops, builds the reflect padding at both
+                  ends, holds back spp's first init_frames frames, and trims
+                  the emitted padded samples to the caller's positions; it
+                  makes no call
+  OnlineEnhancer  a StreamHost and a core, run as soon as input arrives
 
 The wrapper talks to its core through four methods (prime, push, finish,
 reset), so it runs without a device over any object that has them.
+
+``OnlinePool`` (include/cse_online_pool.h) serves streams that do not advance
+in lockstep: they open and close one at a time, each with parameter values
+and a pace of its own, and one step launch advances all that have frames
+pending.  ``PoolCore`` is its device side (cse_pool_init / open / step / close
+/ drop); the pool talks to it through open, step, close and drop.
 """
 
 import ctypes
@@ -171,6 +180,103 @@ class DeviceCore:
         """Nothing to do: the next prime resets every state."""
 
 
+class StreamHost:
+    """The host side of S signals that advance together (a lockstep batch, or
+    with S = 1 one stream of a pool): the reflect head once n_fft/2 + 1 samples
+    are in, buffering to whole hops, holding back spp's first init_frames
+    frames, the reflect tail, and the trimming of emitted padded samples to the
+    caller's positions.  It calls nothing: its owner asks what the device
+    would get now (head, ready, take) and hands back what came out (emitted).
+    """
+
+    def __init__(self, cfg, n_streams=1):
+        self.cfg, self.S = cfg, int(n_streams)
+        self.half = cfg.n_fft // 2
+        self.pre = np.zeros((self.S, 0))     # input before the reflect head exists
+        self.pad = None                      # padded samples the device has not taken
+        self.recent = np.zeros((self.S, 0))  # the last n_fft/2 + 1 input samples
+        self.n_in = 0
+        self.primed = False                  # head() has been taken
+        self.frames = 0                      # frames taken
+        self.at = 0                          # padded samples handed back so far
+        self.returned = 0
+        self.ended = False
+
+    # ------------------------------------------------------------------ input
+    def feed(self, x):
+        """x [S][n] float64, any n >= 0."""
+        half = self.half
+        self.n_in += x.shape[1]
+        self.recent = np.concatenate([self.recent, x], axis=1)[:, -(half + 1):]
+        if self.pad is None:
+            self.pre = np.concatenate([self.pre, x], axis=1)
+            if self.pre.shape[1] >= half + 1:  # xp[0, n_fft/2) = x[n_fft/2], ..., x[1]
+                self.pad = np.concatenate([self.pre[:, half:0:-1], self.pre], axis=1)
+                self.pre = None
+        else:
+            self.pad = np.concatenate([self.pad, x], axis=1)
+
+    def end(self):
+        """The input is complete: the reflect tail follows it.  ValueError, with
+        nothing changed, for an input the path cannot finish."""
+        half, cfg = self.half, self.cfg
+        if self.n_in < half + 1:
+            raise ValueError(f"online: reflect padding of n_fft/2 = {half} samples needs at least "
+                             f"{half + 1} samples (got {self.n_in})")
+        total = 1 + self.n_in // cfg.hop
+        if self.frames == 0 and total < cfg.first_frames:
+            raise ValueError(f"online: the clip has {total} frames, fewer than spp's "
+                             f"init_frames={cfg.first_frames}")
+        # xp[n_fft/2 + len + j] = x[len - 2 - j]
+        self.pad = np.concatenate([self.pad, self.recent[:, -2::-1]], axis=1)
+        self.ended = True
+
+    # ------------------------------------------------------------------ frames
+    def ready(self, max_frames=None):
+        """Frames the device would get now: every whole hop pending, none
+        before the first first_frames frames are; max_frames caps it, but not
+        below those first frames."""
+        cfg = self.cfg
+        if self.pad is None:
+            return 0
+        have = self.pad.shape[1] - (0 if self.primed else cfg.n_fft - cfg.hop)
+        k = max(have, 0) // cfg.hop
+        first = cfg.first_frames if self.frames == 0 else 1
+        if k < first:
+            return 0
+        return k if max_frames is None else min(k, max(int(max_frames), first))
+
+    def head(self):
+        """xp[:, 0:n_fft - hop], what the prime takes, once it exists; None
+        before that and after it has been taken."""
+        nt = self.cfg.n_fft - self.cfg.hop
+        if self.primed or self.pad is None or self.pad.shape[1] < nt:
+            return None
+        head, self.pad = self.pad[:, :nt], self.pad[:, nt:]
+        self.primed = True
+        return head
+
+    def take(self, k):
+        """The next k hop padded samples [S][k hop]; they are the device's now."""
+        n = k * self.cfg.hop
+        x, self.pad = self.pad[:, :n], self.pad[:, n:]
+        self.frames += k
+        return x
+
+    def emitted(self, y):
+        """The next padded samples the device emitted, [S][m] -> the caller's
+        positions among them (padded sample p is output sample p - n_fft/2;
+        once the input has ended, nothing from its length on)."""
+        at, self.at = self.at, self.at + y.shape[1]
+        lo = max(self.half - at, 0)
+        hi = y.shape[1]
+        if self.ended:
+            hi = max(min(self.n_in + self.half - at, hi), lo)
+        out = y[:, lo:hi]
+        self.returned += out.shape[1]
+        return out
+
+
 class OnlineEnhancer:
     """One algorithm and parameter set on n_streams signals in lockstep.
 
@@ -201,20 +307,11 @@ class OnlineEnhancer:
         return self.cfg.n_fft - 1
 
     def reset(self):
-        half = self.cfg.n_fft // 2
-        self._pre = np.zeros((self.S, 0))     # input before the reflect head exists
-        self._pad = None                      # padded samples the core has not taken
-        self._recent = np.zeros((self.S, 0))  # the last n_fft/2 + 1 input samples
-        self._n_in = 0
-        self._primed = False
-        self._frames = 0
-        self._returned = 0
+        self._host = StreamHost(self.cfg, self.S)
         self._finished = False
         self._flat = self.S == 1
-        self._half = half
         self.core.reset()
 
-    # ------------------------------------------------------------------ input
     def _block(self, block):
         x = np.asarray(block, dtype=np.float64)
         if x.ndim == 1:
@@ -222,7 +319,7 @@ class OnlineEnhancer:
                 raise ValueError(f"online: a 1-D block for {self.S} streams")
             x = x[None, :]
         elif x.ndim == 2 and x.shape[0] == self.S:
-            if self._n_in == 0 and self._pre.shape[1] == 0:
+            if self._host.n_in == 0:
                 self._flat = False
         else:
             raise ValueError(f"online: block of shape {x.shape} for {self.S} streams")
@@ -231,73 +328,261 @@ class OnlineEnhancer:
     def push(self, block):
         if self._finished:
             raise RuntimeError("online: push after finish (reset() first)")
-        x = self._block(block)
-        half = self._half
-        self._n_in += x.shape[1]
-        self._recent = np.concatenate([self._recent, x], axis=1)[:, -(half + 1):]
-        if self._pad is None:
-            self._pre = np.concatenate([self._pre, x], axis=1)
-            if self._pre.shape[1] >= half + 1:  # xp[0, n_fft/2) = x[n_fft/2], ..., x[1]
-                self._pad = np.concatenate([self._pre[:, half:0:-1], self._pre], axis=1)
-                self._pre = None
-        else:
-            self._pad = np.concatenate([self._pad, x], axis=1)
-        return self._result(*self._advance(False))
+        self._host.feed(self._block(block))
+        return self._result(*self._advance())
 
     def finish(self):
         if self._finished:
             raise RuntimeError("online: finish after finish (reset() first)")
-        half, cfg = self._half, self.cfg
-        if self._n_in < half + 1:
-            raise ValueError(f"online: reflect padding of n_fft/2 = {half} samples needs at least "
-                             f"{half + 1} samples (got {self._n_in})")
-        # xp[n_fft/2 + len + j] = x[len - 2 - j]
-        self._pad = np.concatenate([self._pad, self._recent[:, -2::-1]], axis=1)
-        y, rows = self._advance(True, length=self._n_in)
+        host = self._host
+        host.end()
+        y, rows = self._advance()
         tail = self.core.finish()
         self._finished = True
-        y = np.concatenate([y, self._trim(tail, self._frames * cfg.hop, self._n_in)], axis=1)
-        assert self._returned == self._n_in, (self._returned, self._n_in)
+        y = np.concatenate([y, host.emitted(tail)], axis=1)
+        assert host.returned == host.n_in, (host.returned, host.n_in)
         return self._result(y, rows)
 
-    # ------------------------------------------------------------------ frames
-    def _advance(self, final, length=None):
-        cfg = self.cfg
+    def _advance(self):
+        """Everything the stream host has for the core now, run at once."""
+        host, cfg = self._host, self.cfg
         empty = (np.zeros((self.S, 0), dtype=np.float32),
                  np.zeros((self.S, 0, cfg.bins), dtype=np.float32))
-        if self._pad is None:
-            return empty
-        if not self._primed:
-            nt = cfg.n_fft - cfg.hop
-            if self._pad.shape[1] < nt:
-                return empty
-            self.core.prime(self._pad[:, :nt])
-            self._pad = self._pad[:, nt:]
-            self._primed = True
-        k = self._pad.shape[1] // cfg.hop
-        if self._frames == 0 and k < cfg.first_frames:
-            if final:
-                raise ValueError(f"online: the clip has {k} frames, fewer than spp's "
-                                 f"init_frames={cfg.first_frames}")
-            return empty
+        head = host.head()
+        if head is not None:
+            self.core.prime(head)
+        k = host.ready()
         if k == 0:
             return empty
-        y, rows = self.core.push(self._pad[:, :k * cfg.hop])
-        self._pad = self._pad[:, k * cfg.hop:]
-        at = self._frames * cfg.hop
-        self._frames += k
-        return self._trim(y, at, length), rows if rows is not None else empty[1]
-
-    def _trim(self, y, at, length):
-        """Emitted padded samples [at, at + m) -> the caller's positions
-        [0, length) among them (padded sample p is output sample p - n_fft/2)."""
-        lo = max(self._half - at, 0)
-        hi = y.shape[1] if length is None else max(min(length + self._half - at, y.shape[1]), lo)
-        out = y[:, lo:hi]
-        self._returned += out.shape[1]
-        return out
+        y, rows = self.core.push(host.take(k))
+        return host.emitted(y), rows if rows is not None else empty[1]
 
     def _result(self, y, rows):
         if self._flat:
             y, rows = y[0], rows[0]
         return (y, rows) if self.want_noise else y
+
+
+def abi_pool_params(cfg):
+    """cse_pool_params_t of a Config: one slot's values."""
+    c = abi_config(cfg)
+    p = _lib.PoolParams()
+    p.param[:] = cfg.param
+    p.mu, p.mcra, p.spp = cfg.mu, c.mcra, c.spp
+    return p
+
+
+class PoolCore:
+    """The device side of a pool (include/cse_online_pool.h): the state block,
+    the work list and the slot table, the handle and its five calls.  Arrays in
+    and out are numpy; every call returns after its results are on the host.
+    No CPU fallback."""
+
+    def __init__(self, cfg, capacity, want_noise=False):
+        import torch
+        self.torch = torch
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.CseError("no GPU visible: the HIP engine has no CPU fallback")
+        self.cfg, self.capacity, self.want_noise = cfg, int(capacity), bool(want_noise)
+        sizes = (int(self.lib.cse_pool_state_bytes(cfg.n_fft, self.capacity)),
+                 int(self.lib.cse_pool_work_bytes(self.capacity)))
+        if min(sizes) < 0:
+            raise _lib.CseError(f"cse_pool_state_bytes({cfg.n_fft}, {self.capacity}) refused")
+        self.state, self.work = (torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+                                 for n in sizes)
+        self.slots = (_lib.PoolSlot * max(self.capacity, 1))()
+        self.handle = _lib.PoolHandle()
+        c = abi_config(cfg)
+        _lib.check(self.lib.cse_pool_init(
+            ctypes.byref(self.handle), ctypes.byref(c), self.capacity,
+            ctypes.c_void_p(self.state.data_ptr()), ctypes.c_void_p(self.work.data_ptr()),
+            ctypes.cast(self.slots, ctypes.c_void_p)), "cse_pool_init")
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def _dev(self, x):
+        return self.torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).cuda()
+
+    def open(self, slot, cfg, head):
+        """Slot ``slot`` starts a stream with cfg's values (a Config of the
+        pool's shape and method) and the input head [n_fft - hop]."""
+        prm = abi_pool_params(cfg)
+        x = self._dev(head)
+        _lib.check(self.lib.cse_pool_open(ctypes.byref(self.handle), int(slot), ctypes.byref(prm),
+                                          ctypes.c_void_p(x.data_ptr()), self._stream()),
+                   "cse_pool_open")
+        self.torch.cuda.current_stream().synchronize()  # x is read until here
+
+    def step(self, items, x):
+        """items: [(slot, k)]; x: their next k hop samples, concatenated in
+        that order.  Returns (samples [sum k hop], rows [sum k][B] or None)."""
+        torch, cfg = self.torch, self.cfg
+        frames = sum(k for _, k in items)
+        lst = (_lib.PoolItem * max(len(items), 1))(*[_lib.PoolItem(int(s), int(k))
+                                                      for s, k in items])
+        xd = self._dev(x)
+        y = torch.empty(max(frames * cfg.hop, 1), dtype=torch.float32, device="cuda")
+        n = (torch.empty((max(frames, 1), cfg.bins), dtype=torch.float32, device="cuda")
+             if self.want_noise else None)
+        _lib.check(self.lib.cse_pool_step(
+            ctypes.byref(self.handle), ctypes.cast(lst, ctypes.c_void_p), len(items),
+            ctypes.c_void_p(xd.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+            None if n is None else ctypes.c_void_p(n.data_ptr()), self._stream()), "cse_pool_step")
+        return (y[:frames * cfg.hop].cpu().numpy(),
+                None if n is None else n[:frames].cpu().numpy())
+
+    def close(self, slot):
+        """The slot's last n_fft - hop padded samples; the slot is free."""
+        cfg = self.cfg
+        y = self.torch.empty(cfg.n_fft - cfg.hop, dtype=self.torch.float32, device="cuda")
+        _lib.check(self.lib.cse_pool_close(ctypes.byref(self.handle), int(slot),
+                                           ctypes.c_void_p(y.data_ptr()), self._stream()),
+                   "cse_pool_close")
+        return y.cpu().numpy()
+
+    def drop(self, slot):
+        _lib.check(self.lib.cse_pool_drop(ctypes.byref(self.handle), int(slot)), "cse_pool_drop")
+
+
+class _PoolStream:
+    def __init__(self, cfg, slot):
+        self.cfg, self.slot = cfg, slot
+        self.host = StreamHost(cfg, 1)
+        self.opened = False  # the core's open has run
+
+
+class OnlinePool:
+    """Streams that come and go on one device state block
+    (include/cse_online_pool.h): one algorithm, shape and noise method per
+    pool, parameter values and pace per stream.
+
+    open(overrides) starts a stream with the pool's params merged with
+    ``overrides`` and returns its id (never reused); feed(sid, block) buffers
+    float64 samples [n], any n >= 0, without device work; step(max_frames)
+    runs, in one launch, every stream that has whole frames pending (its first
+    first_frames frames, afterwards at least one hop), each by all of them
+    (at most max_frames, which does not cut below an spp stream's first
+    init_frames), and returns {sid: samples} of the streams it ran: float32,
+    final, possibly empty; close(sid) runs what that stream still has, the
+    reflect tail and the finish, returns the rest and frees the slot;
+    drop(sid) abandons the stream.  Everything one stream returns,
+    concatenated, has the length of what was fed and is what
+    OnlineEnhancer(algorithm, merged params) returns for that input.
+    want_noise: (samples, rows [k][B]) in place of samples.  core: the object
+    that runs the slots (default: PoolCore on the GPU).
+    """
+
+    SHAPE = ("n_fft", "hop_length", "noise_method")
+
+    def __init__(self, algorithm, params, capacity=1024, want_noise=False, core=None):
+        self.algorithm, self.params = algorithm, dict(params)
+        self.cfg = config(algorithm, params)
+        if capacity != int(capacity) or int(capacity) < 1:
+            raise ValueError(f"online: capacity={capacity} not an integer >= 1")
+        self.capacity = int(capacity)
+        self.want_noise = bool(want_noise)
+        self.core = PoolCore(self.cfg, self.capacity, want_noise) if core is None else core
+        self._free = list(range(self.capacity))  # kept sorted: the lowest slot goes first
+        self._streams = {}
+        self._next = 0
+
+    def __len__(self):
+        return len(self._streams)
+
+    def merged(self, overrides=None):
+        """The pool's params with ``overrides`` over them, and their Config."""
+        over = dict(overrides or {})
+        cfg = self.cfg
+        _, _, names = ALGOS[cfg.algorithm]
+        takes = set(names) | set(DEFAULTS.get(cfg.algorithm, {})) | set(self.params)
+        if cfg.algo >= _lib.ALGO["MMSE"]:
+            takes.add("noise_mu")
+        for key, value in over.items():
+            if key in self.SHAPE:
+                if value != self.params[key]:
+                    raise ValueError(f"online: {key}={value!r} is fixed by the pool "
+                                     f"({self.params[key]!r})")
+            elif key not in takes and not key.startswith(cfg.method + "_"):
+                raise TypeError(f"online: {cfg.algorithm} with {cfg.method} takes no "
+                                f"parameter {key!r}")
+        params = dict(self.params, **over)
+        return params, config(self.algorithm, params)
+
+    def open(self, overrides=None):
+        _, cfg = self.merged(overrides)
+        if not self._free:
+            raise RuntimeError(f"online: the pool is full ({self.capacity} streams)")
+        sid, self._next = self._next, self._next + 1
+        self._streams[sid] = _PoolStream(cfg, self._free.pop(0))
+        return sid
+
+    def _get(self, sid):
+        if sid not in self._streams:
+            raise KeyError(f"online: no open stream {sid!r}")
+        return self._streams[sid]
+
+    def feed(self, sid, block):
+        x = np.asarray(block, dtype=np.float64)
+        if x.ndim != 1:
+            raise ValueError(f"online: block of shape {x.shape} for one stream")
+        self._get(sid).host.feed(x[None, :])
+
+    def step(self, max_frames=None):
+        if max_frames is not None and (max_frames != int(max_frames) or int(max_frames) < 1):
+            raise ValueError(f"online: max_frames={max_frames} not an integer >= 1")
+        run = [(sid, st, st.host.ready(max_frames)) for sid, st in self._streams.items()]
+        return self._run([r for r in run if r[2] > 0])
+
+    def close(self, sid):
+        st = self._get(sid)
+        st.host.end()  # raises, with the stream as it was, for an input that cannot finish
+        k = st.host.ready()
+        y, rows = self._run([(sid, st, k)] if k else [], always=sid)[sid]
+        if st.opened:
+            tail = self.core.close(st.slot)
+            y = np.concatenate([y, st.host.emitted(tail[None, :])[0]])
+        assert st.host.returned == st.host.n_in, (st.host.returned, st.host.n_in)
+        self._release(sid)
+        return (y, rows) if self.want_noise else y
+
+    def drop(self, sid):
+        st = self._get(sid)
+        if st.opened:
+            self.core.drop(st.slot)
+        self._release(sid)
+
+    def _release(self, sid):
+        slot = self._streams.pop(sid).slot
+        self._free.append(slot)
+        self._free.sort()
+
+    def _run(self, run, always=None):
+        """One step of the core for ``run`` = [(sid, stream, k)], after the open
+        of every stream it runs for the first time."""
+        bins = self.cfg.bins
+        outs = {}
+        if always is not None:
+            outs[always] = (np.zeros(0, dtype=np.float32), np.zeros((0, bins), dtype=np.float32))
+        if not run:
+            return outs
+        for _, st, _ in run:
+            head = st.host.head()
+            if head is not None:
+                self.core.open(st.slot, st.cfg, head[0])
+                st.opened = True
+        hop = self.cfg.hop
+        x = np.concatenate([st.host.take(k)[0] for _, st, k in run])
+        y, rows = self.core.step([(st.slot, k) for _, st, k in run], x)
+        at = 0
+        for sid, st, k in run:
+            ys = st.host.emitted(y[None, at * hop:(at + k) * hop])[0]
+            rs = rows[at:at + k] if rows is not None else np.zeros((0, bins), dtype=np.float32)
+            outs[sid] = (ys, rs)
+            at += k
+        if always is None and not self.want_noise:
+            outs = {sid: o[0] for sid, o in outs.items()}
+        return outs
+
+

@@ -105,6 +105,9 @@
  *   nothing and return CSE_OK.
  * cse_online_finish: y_tail [S][n_fft - hop] f32; afterwards push is refused
  *   until the next cse_online_prime.
+ *
+ * Streams that start and end one by one, with parameter values and a pace of
+ * their own: cse_online_pool.h.
  */
 #ifndef CSE_ONLINE_H_
 #define CSE_ONLINE_H_
