@@ -58,10 +58,8 @@ struct Layout {
 };
 
 static Layout layout(int64_t n_sig, int64_t len, int H) {
-    const int hop = H / 16 * 15 / 4;
     Layout L;
-    L.J = len / hop - 4;
-    if (L.J < 0) L.J = 0;
+    L.J = frames_of(len, H / 16 * 15 / 4);
     L.nl = 0;                                      // int n_high, n_mid, n_low, 0 per signal
     L.order = up256(n_sig * 4 * 4);                // int [n_sig][J]: frames ordered by level
     L.lvl = L.order + up256(n_sig * L.J * 4);      // int [n_sig][J]: level of each frame
@@ -69,11 +67,6 @@ static Layout layout(int64_t n_sig, int64_t len, int H) {
     L.spec = L.pxx + up256(n_sig * NL * H * 4);    // f32 complex [n_sig][J][H]
     L.total = L.spec + up256(n_sig * L.J * H * 8);
     return L;
-}
-
-// the sizes the entry points accept (the grid's y dimension; 32-bit frame indices)
-static bool sizes_ok(int64_t n_sig, int64_t len) {
-    return n_sig >= 0 && n_sig <= 65535 && len >= 0 && len < ((int64_t)1 << 36);
 }
 
 // ---------------------------------------------------------------------------
@@ -163,7 +156,7 @@ __global__ void __launch_bounds__(PNT) csii_clean_kernel(const double* __restric
     for (int l = 0; l < L; ++l) base += nl[4 * sig + l];
     const int n = nl[4 * sig + L];
     const int* ord = order + sig * J + base;
-    for (int i = tid; i < C::W; i += PNT) {
+    for (int i = tid; i < C::W; i += PNT) {  // hann_fill, written out (see there)
         double s, c;
         sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
         wnd[i] = 0.5 * (1.0 - c);
@@ -263,7 +256,7 @@ __global__ void __launch_bounds__(NT, 2) csii_cells_kernel(CellArgs a) {
     __shared__ double score[NL];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t cell = blockIdx.x;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = quiet_nan();
     if (a.J < 1) {  // uniform over the grid
         if (tid < 4) a.csii[4 * cell + tid] = nan;
         return;
@@ -272,11 +265,7 @@ __global__ void __launch_bounds__(NT, 2) csii_cells_kernel(CellArgs a) {
     const int lag = a.lag ? a.lag[cell] : 0;
     const float* yc = a.y + a.y_offset[cell];
     const bool clip = a.clip != 0;
-    for (int i = tid; i < C::W; i += NT) {
-        double s, c;
-        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
-        wnd[i] = (float)(0.5 * (1.0 - c));
-    }
+    hann_fill(wnd, C::W, tid, NT);
     stage_filters<float>(a.bands, H, fv, flo, fn, tid, NT);
     Twiddles<float, H> tw;
     tw.init(lane);
@@ -402,25 +391,20 @@ __global__ void __launch_bounds__(NT, 2) csii_cells_kernel(CellArgs a) {
 using namespace cse;
 
 extern "C" int64_t cse_csii_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
-    if (!H || !csii::sizes_ok(n_sig, len)) return -1;
+    const int H = half_bins(sr);
+    if (!H || !sizes_ok(n_sig, len)) return -1;
     return csii::layout(n_sig, len, H).total;
 }
 
 extern "C" int64_t cse_csii_scratch_bytes(int64_t n_cells, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
-    if (!H || n_cells < 0 || len < 0) return -1;
+    if (!half_bins(sr) || n_cells < 0 || len < 0) return -1;
     return 0;
 }
 
 extern "C" int cse_csii_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
                                 void* workspace, cse_stream_t stream) {
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_csii_prepare: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(clean && workspace, "cse_csii_prepare: NULL argument");
-    CSE_CHECK_ARG(n_sig >= 1 && len >= 1 && csii::sizes_ok(n_sig, len),
-                  "cse_csii_prepare: n_sig=%lld (1-65535) len=%lld", (long long)n_sig,
-                  (long long)len);
+    CSE_CHECK_PREPARE_ARGS("cse_csii_prepare", clean, n_sig, len, sr, workspace);
+    const int H = half_bins(sr);
     const csii::Layout L = csii::layout(n_sig, len, H);
     unsigned char* ws = (unsigned char*)workspace;
     int* nl = (int*)(ws + L.nl);
@@ -450,14 +434,10 @@ extern "C" int cse_csii_cells(const float* y, const int64_t* y_offset, const int
                               int sr, int clip, const void* workspace, void* scratch,
                               double* csii_out, cse_stream_t stream) {
     (void)scratch;
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_csii_cells: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(y && y_offset && sig_of && workspace && csii_out, "cse_csii_cells: NULL argument");
-    CSE_CHECK_ARG(n_cells >= 0 && n_cells <= 0x7fffffffLL && n_sig >= 1 && len >= 1 &&
-                      csii::sizes_ok(n_sig, len),
-                  "cse_csii_cells: n_cells=%lld n_sig=%lld len=%lld", (long long)n_cells,
-                  (long long)n_sig, (long long)len);
+    CSE_CHECK_CELLS_ARGS("cse_csii_cells", y && y_offset && sig_of && workspace && csii_out,
+                         n_cells, n_sig, len, sr);
     if (n_cells == 0) return CSE_OK;
+    const int H = half_bins(sr);
     const seg::Bands* sup = seg::band_table(H);
     CSE_CHECK_ARG(sup != nullptr, "cse_csii_cells: filter support too wide");
     const csii::Layout L = csii::layout(n_sig, len, H);

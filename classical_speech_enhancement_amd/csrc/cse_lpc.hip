@@ -34,7 +34,7 @@
 // The clean side (cse_lpc_prepare) runs the same two phases on x and leaves per
 // frame a record of 2P + 3 doubles: silent flag, R_x[0..P], A_x T(R_x) A_x^T,
 // c_x[1..P].
-#include "cse_common.hpp"
+#include "cse_cells.hpp"
 
 #include "../../include/cse_lpc.h"
 
@@ -44,7 +44,6 @@ namespace lpc {
 constexpr int NT = 256;       // threads per workgroup
 constexpr int NW = NT / 64;
 constexpr int CH = 128;       // frames per chunk
-constexpr int NSEL = 1536;    // frames whose values the cell kernel keeps in LDS
 constexpr double K10 = 4.342944819032518;  // 10 / ln 10
 
 template <int SR>
@@ -66,36 +65,6 @@ struct Cfg {
 
 template <class C>
 __device__ __forceinline__ int pidx(int i) { return i + i / C::SPL; }
-
-// ordering of LDS accesses among the lanes of one wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_add(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return v + __hiloint2double(hi, lo);
-}
-
-// sum over each row of 16 lanes, all 64 active; every lane gets its row's sum
-__device__ __forceinline__ double row_sum(double v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-    v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x140>(v);  // row_mirror
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    v = row_sum(v);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 // The windowed frame src(i) w[i], i < W, staged in fb; its autocorrelation
 // R[0..P] written to Rrow.  Returns whether any sample is non-zero.  Called by
@@ -216,13 +185,10 @@ struct Layout {
     int64_t ja, rec, total;  // byte offsets
 };
 
-static inline int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 static Layout layout(int64_t n_sig, int64_t len, int sr) {
     const int hop = sr == 16000 ? 120 : 60, rec = sr == 16000 ? Cfg<16000>::REC : Cfg<8000>::REC;
     Layout L;
-    L.J = len / hop - 4;
-    if (L.J < 0) L.J = 0;
+    L.J = frames_of(len, hop);
     L.ja = 0;  // int ja, n95 per signal
     L.rec = up256(n_sig * 2 * 4);
     L.total = L.rec + up256(n_sig * L.J * rec * 8);
@@ -231,11 +197,7 @@ static Layout layout(int64_t n_sig, int64_t len, int sr) {
 
 template <class C>
 __device__ __forceinline__ void init_frames(double* wnd, double (*fb)[C::FB], int tid) {
-    for (int i = tid; i < C::W; i += NT) {
-        double s, c;
-        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
-        wnd[i] = 0.5 * (1.0 - c);
-    }
+    hann_fill(wnd, C::W, tid, NT);
     for (int e = tid; e < NW * C::P; e += NT) fb[e / C::P][pidx<C>(C::W + e % C::P)] = 0.0;
 }
 
@@ -277,24 +239,6 @@ __global__ void __launch_bounds__(NT) lpc_clean_kernel(const double* __restrict_
     for (int n = 1; n <= C::P; ++n) r[C::R_C + n - 1] = c[n];
 }
 
-__global__ void __launch_bounds__(256) lpc_count_kernel(const double* __restrict__ rec, int64_t J,
-                                                        int rec_len, int* __restrict__ ja) {
-    __shared__ int red[256];
-    const int64_t sig = blockIdx.x;
-    int n = 0;
-    for (int64_t f = threadIdx.x; f < J; f += 256) n += rec[(sig * J + f) * rec_len] == 0.0 ? 1 : 0;
-    red[threadIdx.x] = n;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ja[2 * sig] = red[0];
-        ja[2 * sig + 1] = (int)((19 * (int64_t)red[0] + 10) / 20);  // n95
-    }
-}
-
 // ---------------------------------------------------------------------------
 // cells
 // ---------------------------------------------------------------------------
@@ -312,71 +256,15 @@ struct CellArgs {
     double* cep;
 };
 
-// sample n of a cell's test signal: y shifted by the alignment lag, zero
-// outside [0, len), clipped (cse_stoi.hip's cell_sample)
-__device__ __forceinline__ float cell_sample(const float* y, int64_t n, int64_t len, int lag,
-                                             bool clip) {
+// cell_sample (cse_cells.hpp) with an unconditional load instead of its early
+// return, so that a frame's loads are issued together (see the head comment)
+__device__ __forceinline__ float cell_sample_unbranched(const float* y, int64_t n, int64_t len,
+                                                        int lag, bool clip) {
     const int64_t s = n - lag;
     const bool ok = n >= 0 && n < len && s >= 0 && s < len;
     float v = y[ok ? s : 0];  // an unconditional load: a frame's loads are issued together
     if (clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
     return ok ? v : 0.0f;
-}
-
-// Mean of the k smallest of v[0..n) (all >= 0 or +inf, at least k finite), by
-// the whole workgroup; the result is valid in thread 0.
-__device__ double trimmed_mean(const float* v, int64_t n, unsigned k, unsigned* hist, unsigned* sh,
-                               double* red, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned prefix = 0, mask = 0, need = k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;  // NT == 256 bins
-        __syncthreads();
-        for (int64_t i = tid; i < n; i += NT) {
-            const unsigned b = __float_as_uint(v[i]);
-            if ((b & mask) == prefix) atomicAdd(&hist[(b >> shift) & 255], 1u);
-        }
-        __syncthreads();
-        if (wave == 0) {  // the bin that holds the need-th smallest of the matching values
-            const unsigned h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2],
-                           h3 = hist[4 * lane + 3];
-            const unsigned s = h0 + h1 + h2 + h3;
-            unsigned inc = s;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned t = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += t;
-            }
-            const unsigned long long m = __ballot(inc >= need);
-            if (m != 0 && lane == __ffsll((long long)m) - 1) {
-                unsigned cum = inc - s;
-                int d = 3;
-                if (cum + h0 >= need) d = 0;
-                else if (cum + h0 + h1 >= need) { d = 1; cum += h0; }
-                else if (cum + h0 + h1 + h2 >= need) { d = 2; cum += h0 + h1; }
-                else cum += h0 + h1 + h2;
-                sh[0] = (unsigned)(4 * lane + d);
-                sh[1] = need - cum;
-            }
-        }
-        __syncthreads();
-        prefix |= sh[0] << shift;
-        mask |= 255u << shift;
-        need = sh[1];
-        __syncthreads();  // sh and hist are rewritten by the next pass
-    }
-    double acc = 0.0;
-    for (int64_t i = tid; i < n; i += NT) {
-        const float f = v[i];
-        if (__float_as_uint(f) < prefix) acc += (double)f;
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    const double total = (red[0] + red[1]) + (red[2] + red[3]) +
-                         (double)need * (double)__uint_as_float(prefix);
-    __syncthreads();  // red is reused by the next call
-    return total / (double)k;
 }
 
 template <class C>
@@ -394,10 +282,9 @@ __global__ void __launch_bounds__(NT) lpc_cells_kernel(CellArgs a) {
     const int64_t sig = a.sig_of[cell];
     const int ja = a.ja[2 * sig], n95 = a.ja[2 * sig + 1];
     if (a.J < 1 || ja == 0) {  // uniform over the workgroup
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
         if (tid == 0) {
-            if (a.llr) a.llr[cell] = nan;
-            if (a.cep) a.cep[cell] = nan;
+            if (a.llr) a.llr[cell] = quiet_nan();
+            if (a.cep) a.cep[cell] = quiet_nan();
         }
         return;
     }
@@ -420,8 +307,10 @@ __global__ void __launch_bounds__(NT) lpc_cells_kernel(CellArgs a) {
             const int64_t base = (f0 + fr) * C::HOP;
             frame_autocorr<C>(
                 fb[wave], wnd,
-                [&](int i) { return (double)cell_sample(yc, base + i, a.len, lag, clip); }, lane,
-                Rb[fr]);
+                [&](int i) {
+                    return (double)cell_sample_unbranched(yc, base + i, a.len, lag, clip);
+                },
+                lane, Rb[fr]);
         }
         __syncthreads();
         if (tid < nf) {
@@ -459,19 +348,16 @@ __global__ void __launch_bounds__(NT) lpc_cells_kernel(CellArgs a) {
         __syncthreads();  // Rb is rewritten by the next chunk; the values are complete
     }
     if (want_llr) {
-        const double m = trimmed_mean(vl, a.J, (unsigned)n95, hist, sh, red, tid);
+        const double m =
+            trimmed_mean<NT, wave_sum_shfl>(vl, a.J, (unsigned)n95, hist, sh, red, tid);
         if (tid == 0) a.llr[cell] = m;
     }
     if (want_cep) {
-        const double m = trimmed_mean(vc, a.J, (unsigned)n95, hist, sh, red, tid);
+        const double m =
+            trimmed_mean<NT, wave_sum_shfl>(vc, a.J, (unsigned)n95, hist, sh, red, tid);
         if (tid == 0) a.cep[cell] = m;
     }
 }
-
-static bool rate_ok(int sr) { return sr == 16000 || sr == 8000; }
-
-// f32 values per cell and score in scratch (0: the cell kernel keeps them in LDS)
-static int64_t value_stride(int64_t J) { return J <= NSEL ? 0 : (J + 63) & ~(int64_t)63; }
 
 }  // namespace lpc
 }  // namespace cse
@@ -479,22 +365,18 @@ static int64_t value_stride(int64_t J) { return J <= NSEL ? 0 : (J + 63) & ~(int
 using namespace cse;
 
 extern "C" int64_t cse_lpc_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
-    if (!lpc::rate_ok(sr) || n_sig < 0 || len < 0) return -1;
+    if (!half_bins(sr) || n_sig < 0 || len < 0) return -1;
     return lpc::layout(n_sig, len, sr).total;
 }
 
 extern "C" int64_t cse_lpc_scratch_bytes(int64_t n_cells, int64_t len, int sr) {
-    if (!lpc::rate_ok(sr) || n_cells < 0 || len < 0) return -1;
-    return n_cells * 2 * lpc::value_stride(lpc::layout(1, len, sr).J) * 4;
+    if (!half_bins(sr) || n_cells < 0 || len < 0) return -1;
+    return n_cells * 2 * value_stride(lpc::layout(1, len, sr).J) * 4;
 }
 
 extern "C" int cse_lpc_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
                                void* workspace, cse_stream_t stream) {
-    CSE_CHECK_ARG(lpc::rate_ok(sr), "cse_lpc_prepare: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(clean && workspace, "cse_lpc_prepare: NULL argument");
-    CSE_CHECK_ARG(n_sig >= 1 && n_sig <= 65535 && len >= 1 && len < ((int64_t)1 << 36),
-                  "cse_lpc_prepare: n_sig=%lld (1-65535) len=%lld", (long long)n_sig,
-                  (long long)len);
+    CSE_CHECK_PREPARE_ARGS("cse_lpc_prepare", clean, n_sig, len, sr, workspace);
     const lpc::Layout L = lpc::layout(n_sig, len, sr);
     unsigned char* ws = (unsigned char*)workspace;
     int* ja = (int*)(ws + L.ja);
@@ -509,9 +391,12 @@ extern "C" int cse_lpc_prepare(const double* clean, int64_t n_sig, int64_t len, 
             hipLaunchKernelGGL(lpc::lpc_clean_kernel<lpc::Cfg<8000>>, grid, dim3(lpc::NT), 0, st,
                                clean, len, L.J, rec);
     }
-    hipLaunchKernelGGL(lpc::lpc_count_kernel, dim3((unsigned)n_sig), dim3(256), 0, st,
-                       (const double*)rec, L.J,
-                       sr == 16000 ? lpc::Cfg<16000>::REC : lpc::Cfg<8000>::REC, ja);
+    if (sr == 16000)
+        hipLaunchKernelGGL((count_active_kernel<double, lpc::Cfg<16000>::REC, 0, true>),
+                           dim3((unsigned)n_sig), dim3(256), 0, st, (const double*)rec, L.J, ja);
+    else
+        hipLaunchKernelGGL((count_active_kernel<double, lpc::Cfg<8000>::REC, 0, true>),
+                           dim3((unsigned)n_sig), dim3(256), 0, st, (const double*)rec, L.J, ja);
     CSE_CHECK_LAUNCH("cse_lpc_prepare");
     return CSE_OK;
 }
@@ -520,16 +405,11 @@ extern "C" int cse_lpc_cells(const float* y, const int64_t* y_offset, const int3
                              const int32_t* sig_of, int64_t n_cells, int64_t n_sig, int64_t len,
                              int sr, int clip, const void* workspace, void* scratch, double* llr,
                              double* cep, cse_stream_t stream) {
-    CSE_CHECK_ARG(lpc::rate_ok(sr), "cse_lpc_cells: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(y && y_offset && sig_of && workspace && (llr || cep),
-                  "cse_lpc_cells: NULL argument");
-    CSE_CHECK_ARG(n_cells >= 0 && n_cells <= 0x7fffffffLL && n_sig >= 1 && n_sig <= 65535 &&
-                      len >= 1 && len < ((int64_t)1 << 36),
-                  "cse_lpc_cells: n_cells=%lld n_sig=%lld len=%lld", (long long)n_cells,
-                  (long long)n_sig, (long long)len);
+    CSE_CHECK_CELLS_ARGS("cse_lpc_cells", y && y_offset && sig_of && workspace && (llr || cep),
+                         n_cells, n_sig, len, sr);
     if (n_cells == 0) return CSE_OK;
     const lpc::Layout L = lpc::layout(n_sig, len, sr);
-    const int64_t vstride = lpc::value_stride(L.J);
+    const int64_t vstride = value_stride(L.J);
     CSE_CHECK_ARG(vstride == 0 || scratch,
                   "cse_lpc_cells: %lld frames need scratch (cse_lpc_scratch_bytes)", (long long)L.J);
     const unsigned char* ws = (const unsigned char*)workspace;

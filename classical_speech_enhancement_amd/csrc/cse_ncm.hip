@@ -68,10 +68,8 @@ struct Layout {
 };
 
 static Layout layout(int64_t n_sig, int64_t len, int H) {
-    const int hop = H / 16 * 15 / 4;
     Layout L;
-    L.J = len / hop - 4;
-    if (L.J < 0) L.J = 0;
+    L.J = frames_of(len, H / 16 * 15 / 4);
     L.M = L.J >= TAPS ? (L.J - TAPS) / DEC + 1 : 0;
     L.env = 0;                                        // f64 [n_sig][J][NB]
     L.dx = up256(n_sig * L.J * NB * 8);               // f64 [n_sig][M][NB]
@@ -80,11 +78,6 @@ static Layout layout(int64_t n_sig, int64_t len, int H) {
     L.dead = L.sxx + up256(n_sig * RS * 8);           // int [n_sig][RS]: 1 = the band does not move
     L.total = L.dead + up256(n_sig * RS * 4);
     return L;
-}
-
-// the sizes the entry points accept (the grid's y dimension; 32-bit frame indices)
-static bool sizes_ok(int64_t n_sig, int64_t len) {
-    return n_sig >= 0 && n_sig <= 65535 && len >= 0 && len < ((int64_t)1 << 36);
 }
 
 // ---------------------------------------------------------------------------
@@ -100,7 +93,7 @@ __global__ void __launch_bounds__(PNT) ncm_frames_kernel(const double* __restric
     __shared__ double fv[NB * FWP];
     __shared__ int flo[32], fn[32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < C::W; i += PNT) {
+    for (int i = tid; i < C::W; i += PNT) {  // hann_fill, written out (see there)
         double s, c;
         sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
         wnd[i] = 0.5 * (1.0 - c);
@@ -200,7 +193,7 @@ __global__ void __launch_bounds__(NT, 4) ncm_cells_kernel(CellArgs a) {
     __shared__ float ring[RING * RS];  // e_j[i] of frame j at row j % RING
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t cell = blockIdx.x;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = quiet_nan();
     if (a.M < 2) {  // uniform over the grid
         if (tid < 2) a.out[2 * cell + tid] = nan;
         return;
@@ -209,11 +202,7 @@ __global__ void __launch_bounds__(NT, 4) ncm_cells_kernel(CellArgs a) {
     const int lag = a.lag ? a.lag[cell] : 0;
     const float* yc = a.y + a.y_offset[cell];
     const bool clip = a.clip != 0;
-    for (int i = tid; i < C::W; i += NT) {
-        double s, c;
-        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
-        wnd[i] = (float)(0.5 * (1.0 - c));
-    }
+    hann_fill(wnd, C::W, tid, NT);
     stage_filters<float>(a.bands, H, fv, flo, fn, tid, NT);
     Twiddles<float, H> tw;
     tw.init(lane);
@@ -304,25 +293,20 @@ __global__ void __launch_bounds__(NT, 4) ncm_cells_kernel(CellArgs a) {
 using namespace cse;
 
 extern "C" int64_t cse_ncm_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
-    if (!H || !ncm::sizes_ok(n_sig, len)) return -1;
+    const int H = half_bins(sr);
+    if (!H || !sizes_ok(n_sig, len)) return -1;
     return ncm::layout(n_sig, len, H).total;
 }
 
 extern "C" int64_t cse_ncm_scratch_bytes(int64_t n_cells, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
-    if (!H || n_cells < 0 || len < 0) return -1;
+    if (!half_bins(sr) || n_cells < 0 || len < 0) return -1;
     return 0;
 }
 
 extern "C" int cse_ncm_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
                                void* workspace, cse_stream_t stream) {
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_ncm_prepare: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(clean && workspace, "cse_ncm_prepare: NULL argument");
-    CSE_CHECK_ARG(n_sig >= 1 && len >= 1 && ncm::sizes_ok(n_sig, len),
-                  "cse_ncm_prepare: n_sig=%lld (1-65535) len=%lld", (long long)n_sig,
-                  (long long)len);
+    CSE_CHECK_PREPARE_ARGS("cse_ncm_prepare", clean, n_sig, len, sr, workspace);
+    const int H = half_bins(sr);
     const seg::Bands* sup = seg::band_table(H);
     CSE_CHECK_ARG(sup != nullptr, "cse_ncm_prepare: filter support too wide");
     const ncm::Layout L = ncm::layout(n_sig, len, H);
@@ -352,13 +336,9 @@ extern "C" int cse_ncm_cells(const float* y, const int64_t* y_offset, const int3
                              int sr, int clip, const void* workspace, void* scratch,
                              double bif_power, double* ncm_out, cse_stream_t stream) {
     (void)scratch;
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_ncm_cells: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(y && y_offset && sig_of && workspace && ncm_out, "cse_ncm_cells: NULL argument");
-    CSE_CHECK_ARG(n_cells >= 0 && n_cells <= 0x7fffffffLL && n_sig >= 1 && len >= 1 &&
-                      ncm::sizes_ok(n_sig, len),
-                  "cse_ncm_cells: n_cells=%lld n_sig=%lld len=%lld", (long long)n_cells,
-                  (long long)n_sig, (long long)len);
+    CSE_CHECK_CELLS_ARGS("cse_ncm_cells", y && y_offset && sig_of && workspace && ncm_out, n_cells,
+                         n_sig, len, sr);
+    const int H = half_bins(sr);
     CSE_CHECK_ARG(std::isfinite(bif_power) && bif_power >= 0.0,
                   "cse_ncm_cells: bif_power=%g (finite, >= 0)", bif_power);
     if (n_cells == 0) return CSE_OK;

@@ -3,10 +3,12 @@
 // 30-ms frames of include/cse_segsnr.h, one wave per frame: the NFFT-point transform of the
 // zero-padded windowed frame and the 25 critical-band sums over the filter
 // supports.  The comments at the head of cse_segsnr.hip describe the scheme.
+// What is not about the transform (window, cell samples, counts, checks) is in
+// cse_cells.hpp.
 #ifndef CSE_SEGFFT_HPP_
 #define CSE_SEGFFT_HPP_
 
-#include "cse_common.hpp"
+#include "cse_cells.hpp"
 
 namespace cse {
 namespace seg {
@@ -84,38 +86,6 @@ __device__ __forceinline__ void dft(cx<T> (&v)[8]) {
     v[3] = d1;
     v[5] = d2;
     v[7] = d3;
-}
-
-// ordering of LDS accesses among the lanes of one wave (the LDS executes a
-// wave's DS instructions in issue order: a compiler-level barrier suffices)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Sum over the 64 lanes of a wave, all active; every lane gets the result.
-// Within a row of 16 lanes by DPP (quad swaps, then the half-row and row
-// mirrors), the four row sums by v_readlane: no LDS traffic, where
-// __shfl_xor costs two ds_bpermute per step for a double.
-template <int CTRL>
-__device__ __forceinline__ double dpp_add(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return v + __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double row_sum_of(double v, int lane) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                            __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-    v = dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x140>(v);  // row_mirror
-    return (row_sum_of(v, 0) + row_sum_of(v, 16)) + (row_sum_of(v, 32) + row_sum_of(v, 48));
 }
 
 __device__ __forceinline__ int pad(int i) { return i + (i >> 3); }
@@ -289,21 +259,6 @@ __host__ __device__ inline double filter_entry(int i, int k, int H) {
     const double q = ((double)k - f0) / bw;
     return exp(-11.0 * (q * q) + log(band[0]) - log(band[i]));
 }
-
-static inline int64_t up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-// sample n of a cell's test signal: y shifted by the alignment lag, zero
-// outside [0, len), clipped (cse_stoi.hip's cell_sample)
-__device__ __forceinline__ float cell_sample(const float* y, int64_t n, int64_t len, int lag,
-                                             bool clip) {
-    const int64_t s = n - lag;
-    if (n < 0 || n >= len || s < 0 || s >= len) return 0.0f;
-    float v = y[s];
-    if (clip) v = fminf(fmaxf(v, -1.0f), 1.0f);
-    return v;
-}
-
-static inline int half_bins(int sr) { return sr == 16000 ? 512 : (sr == 8000 ? 256 : 0); }
 
 // the supports of the filter rows (the entries above the floor), on the host
 static inline bool band_supports(int H, Bands* b) {

@@ -28,7 +28,9 @@
 // (f32) and s (f64).  The cell kernel never transforms x.
 //
 // The frame code itself (transform, magnitudes, band sums, filter table) is in
-// cse_segfft.hpp, shared with cse_wss.hip.
+// cse_segfft.hpp, shared with cse_wss.hip, cse_csii.hip and cse_ncm.hip; the
+// window, the cell samples, the frame count and the entry points' checks are
+// in cse_cells.hpp, shared with cse_lpc.hip as well.
 #include "cse_segfft.hpp"
 
 #include "../../include/cse_segsnr.h"
@@ -52,10 +54,8 @@ struct Layout {
 };
 
 static Layout layout(int64_t n_sig, int64_t len, int H) {
-    const int hop = H / 16 * 15 / 4;
     Layout L;
-    L.J = len / hop - 4;
-    if (L.J < 0) L.J = 0;
+    L.J = frames_of(len, H / 16 * 15 / 4);
     L.filt = 0;  // int lo[32], int n[32], float vals[NB][FW]
     L.ja = up256(64 * 4 + NB * FW * 4);
     L.x32 = L.ja + up256(n_sig * 4);
@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(PNT) segsnr_clean_kernel(const double* __restr
     __shared__ double fv[NB * FWP];
     __shared__ int flo[32], fn[32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < C::W; i += PNT) {
+    for (int i = tid; i < C::W; i += PNT) {  // hann_fill, written out (see there)
         double s, c;
         sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
         wnd[i] = 0.5 * (1.0 - c);
@@ -152,22 +152,6 @@ __global__ void __launch_bounds__(PNT) segsnr_clean_kernel(const double* __restr
     }
 }
 
-__global__ void __launch_bounds__(256) segsnr_count_kernel(const float* __restrict__ rec, int64_t J,
-                                                           int* __restrict__ ja) {
-    __shared__ int red[256];
-    const int64_t sig = blockIdx.x;
-    int n = 0;
-    for (int64_t f = threadIdx.x; f < J; f += 256)
-        n += rec[(sig * J + f) * REC + R_SILENT] == 0.0f ? 1 : 0;
-    red[threadIdx.x] = n;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ja[sig] = red[0];
-}
-
 // ---------------------------------------------------------------------------
 // cells
 // ---------------------------------------------------------------------------
@@ -208,11 +192,7 @@ __global__ void __launch_bounds__(NT, 4) segsnr_cells_kernel(CellArgs a) {
     const float* yc = a.y + a.y_offset[cell];
     const float* xc = a.x32 + sig * a.len;
     const bool clip = a.clip != 0, want_fw = a.fw != nullptr;
-    for (int i = tid; i < C::W; i += NT) {
-        double s, c;
-        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
-        wnd[i] = (float)(0.5 * (1.0 - c));
-    }
+    hann_fill(wnd, C::W, tid, NT);
     if (tid < 32) {
         flo[tid] = a.flo[tid];
         fn[tid] = a.fn[tid];
@@ -310,9 +290,8 @@ __global__ void __launch_bounds__(NT, 4) segsnr_cells_kernel(CellArgs a) {
     const double s0 = wave_sum(seg_acc), s1 = wave_sum(fw_acc);
     if (tid == 0) {
         const int ja = a.ja[sig];
-        const double nan = __longlong_as_double(0x7ff8000000000000LL);
-        if (a.seg) a.seg[cell] = ja > 0 ? s0 / (double)ja : nan;
-        if (a.fw) a.fw[cell] = ja > 0 ? s1 / (double)ja : nan;
+        if (a.seg) a.seg[cell] = ja > 0 ? s0 / (double)ja : quiet_nan();
+        if (a.fw) a.fw[cell] = ja > 0 ? s1 / (double)ja : quiet_nan();
     }
 }
 
@@ -322,24 +301,20 @@ __global__ void __launch_bounds__(NT, 4) segsnr_cells_kernel(CellArgs a) {
 using namespace cse;
 
 extern "C" int64_t cse_segsnr_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
+    const int H = half_bins(sr);
     if (!H || n_sig < 0 || len < 0) return -1;
     return seg::layout(n_sig, len, H).total;
 }
 
 extern "C" int64_t cse_segsnr_scratch_bytes(int64_t n_cells, int64_t len, int sr) {
-    if (!seg::half_bins(sr) || n_cells < 0 || len < 0) return -1;
+    if (!half_bins(sr) || n_cells < 0 || len < 0) return -1;
     return 0;  // the cell kernel keeps its intermediates in LDS and registers
 }
 
 extern "C" int cse_segsnr_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
                                   void* workspace, cse_stream_t stream) {
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_segsnr_prepare: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(clean && workspace, "cse_segsnr_prepare: NULL argument");
-    CSE_CHECK_ARG(n_sig >= 1 && n_sig <= 65535 && len >= 1 && len < ((int64_t)1 << 36),
-                  "cse_segsnr_prepare: n_sig=%lld (1-65535) len=%lld", (long long)n_sig,
-                  (long long)len);
+    CSE_CHECK_PREPARE_ARGS("cse_segsnr_prepare", clean, n_sig, len, sr, workspace);
+    const int H = half_bins(sr);
     seg::Bands bands;
     CSE_CHECK_ARG(seg::band_supports(H, &bands), "cse_segsnr_prepare: filter support too wide");
     const seg::Layout L = seg::layout(n_sig, len, H);
@@ -365,8 +340,8 @@ extern "C" int cse_segsnr_prepare(const double* clean, int64_t n_sig, int64_t le
             hipLaunchKernelGGL(seg::segsnr_clean_kernel<256>, grid, dim3(seg::PNT), 0, st, clean,
                                len, L.J, bands, rec);
     }
-    hipLaunchKernelGGL(seg::segsnr_count_kernel, dim3((unsigned)n_sig), dim3(256), 0, st,
-                       (const float*)rec, L.J, ja);
+    hipLaunchKernelGGL((count_active_kernel<float, seg::REC, seg::R_SILENT, false>),
+                       dim3((unsigned)n_sig), dim3(256), 0, st, (const float*)rec, L.J, ja);
     CSE_CHECK_LAUNCH("cse_segsnr_prepare");
     return CSE_OK;
 }
@@ -376,15 +351,11 @@ extern "C" int cse_segsnr_cells(const float* y, const int64_t* y_offset, const i
                                 int sr, int clip, const void* workspace, void* scratch,
                                 double* segsnr, double* fwsegsnr, cse_stream_t stream) {
     (void)scratch;
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_segsnr_cells: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(y && y_offset && sig_of && workspace && (segsnr || fwsegsnr),
-                  "cse_segsnr_cells: NULL argument");
-    CSE_CHECK_ARG(n_cells >= 0 && n_cells <= 0x7fffffffLL && n_sig >= 1 && n_sig <= 65535 &&
-                      len >= 1 && len < ((int64_t)1 << 36),
-                  "cse_segsnr_cells: n_cells=%lld n_sig=%lld len=%lld", (long long)n_cells,
-                  (long long)n_sig, (long long)len);
+    CSE_CHECK_CELLS_ARGS("cse_segsnr_cells",
+                         y && y_offset && sig_of && workspace && (segsnr || fwsegsnr), n_cells,
+                         n_sig, len, sr);
     if (n_cells == 0) return CSE_OK;
+    const int H = half_bins(sr);
     const seg::Layout L = seg::layout(n_sig, len, H);
     const unsigned char* ws = (const unsigned char*)workspace;
     seg::CellArgs a;

@@ -18,7 +18,7 @@
 //
 // Trimmed mean: a frame's value is kept as f32, in LDS while J <= NSEL, in the
 // caller's scratch beyond.  The values are >= 0, so their bit patterns order
-// like the values and cse_lpc.hip's radix select applies: four passes of an
+// like the values and trimmed_mean (cse_cells.hpp) applies: four passes of an
 // 8-bit histogram find the n95-th smallest value t, and the sum of the n95
 // smallest is the sum of the values below t plus the missing count times t.
 // Silent frames hold +inf and are never reached.
@@ -40,7 +40,6 @@ constexpr int REC = 52;       // f32 words per frame record
 constexpr int R_W = NB, R_SILENT = NB + NS;
 constexpr int PNT = 256;      // clean-side kernel: threads per workgroup
 constexpr int PNW = PNT / 64;
-constexpr int NSEL = 1536;    // frames whose values the cell kernel keeps in LDS
 constexpr double E_FLOOR = 1e-10;
 
 // E_i of the band sum e_i.  The product is rounded on its own: contracted into
@@ -93,28 +92,12 @@ struct Layout {
 };
 
 static Layout layout(int64_t n_sig, int64_t len, int H) {
-    const int hop = H / 16 * 15 / 4;
     Layout L;
-    L.J = len / hop - 4;
-    if (L.J < 0) L.J = 0;
+    L.J = frames_of(len, H / 16 * 15 / 4);
     L.ja = 0;  // int ja, n95 per signal
     L.rec = up256(n_sig * 2 * 4);
     L.total = L.rec + up256(n_sig * L.J * REC * 4);
     return L;
-}
-
-// the filter rows over their supports, and the supports, into LDS
-template <typename T>
-__device__ __forceinline__ void load_filters(const Bands& bands, int H, T* fv, int* flo, int* fn,
-                                             int tid, int nt) {
-    if (tid < 32) {
-        flo[tid] = tid < NB ? bands.lo[tid] : 0;
-        fn[tid] = tid < NB ? bands.n[tid] : 0;
-    }
-    for (int e = tid; e < NB * FW; e += nt) {
-        const int i = e / FW, c = e % FW;
-        fv[i * FWP + c] = c < bands.n[i] ? (T)filter_entry(i, bands.lo[i] + c, H) : (T)0;
-    }
 }
 
 template <int H>
@@ -127,12 +110,12 @@ __global__ void __launch_bounds__(PNT) wss_clean_kernel(const double* __restrict
     __shared__ double fv[NB * FWP];
     __shared__ int flo[32], fn[32];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < C::W; i += PNT) {
+    for (int i = tid; i < C::W; i += PNT) {  // hann_fill, written out (see there)
         double s, c;
         sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
         wnd[i] = 0.5 * (1.0 - c);
     }
-    load_filters<double>(bands, H, fv, flo, fn, tid, PNT);
+    stage_filters<double>(bands, H, fv, flo, fn, tid, PNT);
     __syncthreads();
     const int64_t f = (int64_t)blockIdx.x * PNW + wave;
     if (f >= J) return;  // wave-uniform; no workgroup barrier below
@@ -169,25 +152,6 @@ __global__ void __launch_bounds__(PNT) wss_clean_kernel(const double* __restrict
     if (lane >= R_SILENT && lane < REC) r[lane] = 0.0f;
 }
 
-__global__ void __launch_bounds__(256) wss_count_kernel(const float* __restrict__ rec, int64_t J,
-                                                        int* __restrict__ ja) {
-    __shared__ int red[256];
-    const int64_t sig = blockIdx.x;
-    int n = 0;
-    for (int64_t f = threadIdx.x; f < J; f += 256)
-        n += rec[(sig * J + f) * REC + R_SILENT] == 0.0f ? 1 : 0;
-    red[threadIdx.x] = n;
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ja[2 * sig] = red[0];
-        ja[2 * sig + 1] = (int)((19 * (int64_t)red[0] + 10) / 20);  // n95
-    }
-}
-
 // ---------------------------------------------------------------------------
 // cells
 // ---------------------------------------------------------------------------
@@ -204,62 +168,6 @@ struct CellArgs {
     float* scratch;
     double* wss;
 };
-
-// Mean of the k smallest of v[0..n) (all >= 0 or +inf, at least k finite), by
-// the whole workgroup; the result is valid in thread 0.  (cse_lpc.hip's, for
-// NT threads.)
-__device__ double trimmed_mean(const float* v, int64_t n, unsigned k, unsigned* hist, unsigned* sh,
-                               double* red, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned prefix = 0, mask = 0, need = k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        for (int64_t i = tid; i < n; i += NT) {
-            const unsigned b = __float_as_uint(v[i]);
-            if ((b & mask) == prefix) atomicAdd(&hist[(b >> shift) & 255], 1u);
-        }
-        __syncthreads();
-        if (wave == 0) {  // the bin that holds the need-th smallest of the matching values
-            const unsigned h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2],
-                           h3 = hist[4 * lane + 3];
-            const unsigned s = h0 + h1 + h2 + h3;
-            unsigned inc = s;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned t = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += t;
-            }
-            const unsigned long long m = __ballot(inc >= need);
-            if (m != 0 && lane == __ffsll((long long)m) - 1) {
-                unsigned cum = inc - s;
-                int d = 3;
-                if (cum + h0 >= need) d = 0;
-                else if (cum + h0 + h1 >= need) { d = 1; cum += h0; }
-                else if (cum + h0 + h1 + h2 >= need) { d = 2; cum += h0 + h1; }
-                else cum += h0 + h1 + h2;
-                sh[0] = (unsigned)(4 * lane + d);
-                sh[1] = need - cum;
-            }
-        }
-        __syncthreads();
-        prefix |= sh[0] << shift;
-        mask |= 255u << shift;
-        need = sh[1];
-        __syncthreads();  // sh and hist are rewritten by the next pass
-    }
-    double acc = 0.0;
-    for (int64_t i = tid; i < n; i += NT) {
-        const float f = v[i];
-        if (__float_as_uint(f) < prefix) acc += (double)f;
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    double total = (double)need * (double)__uint_as_float(prefix);
-    for (int w = 0; w < NW; ++w) total += red[w];
-    return total / (double)k;
-}
 
 template <int H>
 __global__ void __launch_bounds__(NT, 4) wss_cells_kernel(CellArgs a) {
@@ -283,19 +191,15 @@ __global__ void __launch_bounds__(NT, 4) wss_cells_kernel(CellArgs a) {
     const int64_t sig = a.sig_of[cell];
     const int ja = a.ja[2 * sig], n95 = a.ja[2 * sig + 1];
     if (a.J < 1 || ja == 0) {  // uniform over the workgroup
-        if (tid == 0) a.wss[cell] = __longlong_as_double(0x7ff8000000000000LL);
+        if (tid == 0) a.wss[cell] = quiet_nan();
         return;
     }
     const int lag = a.lag ? a.lag[cell] : 0;
     const float* yc = a.y + a.y_offset[cell];
     const bool clip = a.clip != 0;
     float* vals = a.J <= NSEL ? sv : a.scratch + cell * a.vstride;
-    for (int i = tid; i < C::W; i += NT) {
-        double s, c;
-        sincospi(2.0 * (double)(i + 1) / (double)(C::W + 1), &s, &c);
-        wnd[i] = (float)(0.5 * (1.0 - c));
-    }
-    load_filters<float>(a.bands, H, fv, flo, fn, tid, NT);
+    hann_fill(wnd, C::W, tid, NT);
+    stage_filters<float>(a.bands, H, fv, flo, fn, tid, NT);
     Twiddles<float, H> tw;
     tw.init(lane);
     for (int64_t f0 = 0; f0 < a.J; f0 += FCH) {
@@ -367,24 +271,8 @@ __global__ void __launch_bounds__(NT, 4) wss_cells_kernel(CellArgs a) {
         }
     }
     __syncthreads();  // the values are complete
-    const double m = trimmed_mean(vals, a.J, (unsigned)n95, hist, sh, red, tid);
+    const double m = trimmed_mean<NT>(vals, a.J, (unsigned)n95, hist, sh, red, tid);
     if (tid == 0) a.wss[cell] = m;
-}
-
-// f32 values per cell in scratch (0: the cell kernel keeps them in LDS)
-static int64_t value_stride(int64_t J) { return J <= NSEL ? 0 : (J + 63) & ~(int64_t)63; }
-
-// the filter supports of a rate, made once (12,800 exponentials on the host);
-// NULL when a row is wider than its room
-static const Bands* supports(int H) {
-    struct Table {
-        Bands b;
-        bool ok;
-        explicit Table(int h) { ok = band_supports(h, &b); }
-    };
-    static const Table t512(512), t256(256);
-    const Table& t = H == 512 ? t512 : t256;
-    return t.ok ? &t.b : nullptr;
 }
 
 }  // namespace wss
@@ -393,26 +281,22 @@ static const Bands* supports(int H) {
 using namespace cse;
 
 extern "C" int64_t cse_wss_workspace_bytes(int64_t n_sig, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
+    const int H = half_bins(sr);
     if (!H || n_sig < 0 || len < 0) return -1;
     return wss::layout(n_sig, len, H).total;
 }
 
 extern "C" int64_t cse_wss_scratch_bytes(int64_t n_cells, int64_t len, int sr) {
-    const int H = seg::half_bins(sr);
+    const int H = half_bins(sr);
     if (!H || n_cells < 0 || len < 0) return -1;
-    return n_cells * wss::value_stride(wss::layout(1, len, H).J) * 4;
+    return n_cells * value_stride(wss::layout(1, len, H).J) * 4;
 }
 
 extern "C" int cse_wss_prepare(const double* clean, int64_t n_sig, int64_t len, int sr,
                                void* workspace, cse_stream_t stream) {
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_wss_prepare: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(clean && workspace, "cse_wss_prepare: NULL argument");
-    CSE_CHECK_ARG(n_sig >= 1 && n_sig <= 65535 && len >= 1 && len < ((int64_t)1 << 36),
-                  "cse_wss_prepare: n_sig=%lld (1-65535) len=%lld", (long long)n_sig,
-                  (long long)len);
-    const seg::Bands* sup = wss::supports(H);
+    CSE_CHECK_PREPARE_ARGS("cse_wss_prepare", clean, n_sig, len, sr, workspace);
+    const int H = half_bins(sr);
+    const seg::Bands* sup = seg::band_table(H);
     CSE_CHECK_ARG(sup != nullptr, "cse_wss_prepare: filter support too wide");
     const seg::Bands bands = *sup;
     const wss::Layout L = wss::layout(n_sig, len, H);
@@ -431,8 +315,8 @@ extern "C" int cse_wss_prepare(const double* clean, int64_t n_sig, int64_t len, 
             hipLaunchKernelGGL(wss::wss_clean_kernel<256>, grid, dim3(wss::PNT), 0, st, clean, len,
                                L.J, bands, rec);
     }
-    hipLaunchKernelGGL(wss::wss_count_kernel, dim3((unsigned)n_sig), dim3(256), 0, st,
-                       (const float*)rec, L.J, ja);
+    hipLaunchKernelGGL((count_active_kernel<float, wss::REC, wss::R_SILENT, true>),
+                       dim3((unsigned)n_sig), dim3(256), 0, st, (const float*)rec, L.J, ja);
     CSE_CHECK_LAUNCH("cse_wss_prepare");
     return CSE_OK;
 }
@@ -441,20 +325,16 @@ extern "C" int cse_wss_cells(const float* y, const int64_t* y_offset, const int3
                              const int32_t* sig_of, int64_t n_cells, int64_t n_sig, int64_t len,
                              int sr, int clip, const void* workspace, void* scratch, double* wss_out,
                              cse_stream_t stream) {
-    const int H = seg::half_bins(sr);
-    CSE_CHECK_ARG(H != 0, "cse_wss_cells: sr=%d not supported (16000, 8000)", sr);
-    CSE_CHECK_ARG(y && y_offset && sig_of && workspace && wss_out, "cse_wss_cells: NULL argument");
-    CSE_CHECK_ARG(n_cells >= 0 && n_cells <= 0x7fffffffLL && n_sig >= 1 && n_sig <= 65535 &&
-                      len >= 1 && len < ((int64_t)1 << 36),
-                  "cse_wss_cells: n_cells=%lld n_sig=%lld len=%lld", (long long)n_cells,
-                  (long long)n_sig, (long long)len);
+    CSE_CHECK_CELLS_ARGS("cse_wss_cells", y && y_offset && sig_of && workspace && wss_out, n_cells,
+                         n_sig, len, sr);
     if (n_cells == 0) return CSE_OK;
+    const int H = half_bins(sr);
     const wss::Layout L = wss::layout(n_sig, len, H);
-    const int64_t vstride = wss::value_stride(L.J);
+    const int64_t vstride = value_stride(L.J);
     CSE_CHECK_ARG(vstride == 0 || scratch,
                   "cse_wss_cells: %lld frames need scratch (cse_wss_scratch_bytes)", (long long)L.J);
     const unsigned char* ws = (const unsigned char*)workspace;
-    const seg::Bands* sup = wss::supports(H);
+    const seg::Bands* sup = seg::band_table(H);
     CSE_CHECK_ARG(sup != nullptr, "cse_wss_cells: filter support too wide");
     wss::CellArgs a;
     a.bands = *sup;

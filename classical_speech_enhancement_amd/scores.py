@@ -9,9 +9,12 @@ for every family what was once written out per family.  STOI is not a family:
 it owns column 3 of every table and the ``extended`` switch.  Host-only, like
 trackers.py and layout.py: neither torch nor a loaded library.
 
-A further family touches: its header and .hip file, the build's source list, a
-plan class in metrics.py (with calculate_<name> for each of its names), one
-record here, one keyword in each public signature, and its tests and documents.
+A further family touches: its header and .hip file (which starts from
+csrc/cse_cells.hpp: the frames, the window, a cell's samples, the frame count,
+the trimmed mean and the entry points' argument checks; csrc/cse_segfft.hpp on
+top of it for the critical-band transform), the build's source list, a plan
+class in metrics.py (with calculate_<name> for each of its names), one record
+here, one keyword in each public signature, and its tests and documents.
 """
 
 from collections import OrderedDict
