@@ -1,5 +1,5 @@
 """ctypes binding of libcse.so (the C ABI declared in include/cse.h,
-include/cse_estoi.h, include/cse_mcra.h, include/cse_segsnr.h,
+include/cse_estoi.h, include/cse_stoi_stages.h, include/cse_mcra.h, include/cse_segsnr.h,
 include/cse_spp.h, include/cse_minstat.h, include/cse_imcra.h, include/cse_lpc.h,
 include/cse_wss.h, include/cse_sisdr.h, include/cse_logerr.h, include/cse_csii.h,
 include/cse_ncm.h, include/cse_online.h and include/cse_online_pool.h).
@@ -179,6 +179,12 @@ EXPORTS = ("cse_version", "cse_last_error", "cse_cells_per_group", "cse_stft",
            "cse_stoi_workspace_bytes", "cse_stoi_scratch_bytes", "cse_stoi_prepare",
            "cse_stoi_cells", "cse_stoi_workspace_bytes_sr", "cse_stoi_scratch_bytes_sr",
            "cse_stoi_cells_sr")
+# include/cse_stoi_stages.h, a header of its own (cse.h's code is part of the
+# enhance kernels' pinned source digest): where STOI's stages lie in a workspace
+EXPORTS_STOI_STAGES = ("cse_stoi_layout",)
+# cse_stoi_layout's out, in order: byte offsets, sizes, constants
+STOI_LAYOUT_FIELDS = ("coef64", "meta", "x10", "en", "kf", "btab", "xtob", "xstat", "hgen", "xcol",
+                      "total", "n10", "F", "Mmax", "Jmax", "NBLK", "BT", "META", "MAXD", "FB", "ntap")
 # include/cse_estoi.h (extended STOI), a header of its own: EXPORTS is what cse.h declares
 EXPORTS_ESTOI = ("cse_estoi_workspace_bytes", "cse_estoi_prepare", "cse_estoi_cells")
 # the waveform scores that share one interface, each with a header of its own,
@@ -304,6 +310,8 @@ def load(path=LIB_PATH):
     lib.cse_stoi_scratch_bytes_sr.argtypes = [i64, i64, i32]
     lib.cse_stoi_cells_sr.restype = i32
     lib.cse_stoi_cells_sr.argtypes = [P, P, P, P, i64, i64, i64, i32, i32, P, P, P, P]
+    lib.cse_stoi_layout.restype = i32
+    lib.cse_stoi_layout.argtypes = [i64, i64, i32, i32, P, i32]
     lib.cse_estoi_workspace_bytes.restype = i64
     lib.cse_estoi_workspace_bytes.argtypes = [i64, i64, i32]
     lib.cse_estoi_prepare.restype = i32

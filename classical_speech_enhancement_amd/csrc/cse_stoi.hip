@@ -46,6 +46,7 @@
 // outputs themselves are f32 (the enhance kernel's output type).
 #include "cse_common.hpp"
 #include "cse_estoi.h"
+#include "cse_stoi_stages.h"
 
 #include <math.h>
 #include <numeric>
@@ -1197,6 +1198,27 @@ extern "C" int64_t cse_stoi_workspace_bytes_sr(int64_t n_sig, int64_t len, int s
 
 extern "C" int64_t cse_stoi_workspace_bytes(int64_t n_sig, int64_t len) {
     return cse_stoi_workspace_bytes_sr(n_sig, len, 16000);
+}
+
+// where the stages of the clean side lie in a workspace (host only: for tests
+// and tools that read them back; nothing is launched)
+extern "C" int cse_stoi_layout(int64_t n_sig, int64_t len, int sr, int extended, int64_t* out,
+                               int n_out) {
+    CSE_CHECK_ARG(out, "cse_stoi_layout: NULL out");
+    CSE_CHECK_ARG(n_sig >= 1 && len >= 1, "cse_stoi_layout: n_sig=%lld len=%lld",
+                  (long long)n_sig, (long long)len);
+    CSE_CHECK_ARG(stoi_rate_ok(sr, len), "cse_stoi_layout: sr=%d not supported", sr);
+    CSE_CHECK_ARG(n_out >= CSE_STOI_LAYOUT_N, "cse_stoi_layout: n_out=%d (< %d)", n_out,
+                  CSE_STOI_LAYOUT_N);
+    const StoiLayout L = stoi_layout(n_sig, len, sr);
+    const int64_t xcol = extended ? L.total : -1;
+    const int64_t total = extended ? L.total + align256(n_sig * L.Jmax * stoi::NSEG * 16) : L.total;
+    const int64_t v[CSE_STOI_LAYOUT_N] = {
+        L.coef64, L.meta, L.x10, L.en, L.kf, L.btab, L.xtob, L.xstat, L.hgen, xcol, total,
+        L.n10, L.F, L.Mmax, L.Jmax, L.NBLK, stoi::BT, stoi::META, stoi::MAXD, stoi::FB,
+        sr == 16000 ? 0 : 2 * resamp_for(sr, len).half + 1};
+    for (int i = 0; i < CSE_STOI_LAYOUT_N; ++i) out[i] = v[i];
+    return CSE_OK;
 }
 
 extern "C" int64_t cse_stoi_scratch_bytes_sr(int64_t n_cells, int64_t len, int sr) {

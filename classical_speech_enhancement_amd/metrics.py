@@ -226,6 +226,65 @@ class StoiPlan:
         """score_async, synchronised; NaN entries are pystoi failures (None)."""
         return self.score_async(y, y_offset, sig_of, lag, clip).cpu().numpy()
 
+    def layout(self):
+        """cse_stoi_layout of this plan's workspace: name -> byte offset, size
+        or constant (_lib.STOI_LAYOUT_FIELDS)."""
+        out = np.zeros(len(_lib.STOI_LAYOUT_FIELDS), dtype=np.int64)
+        _lib.check(self.lib.cse_stoi_layout(self.S, self.L, self.sr, int(self.extended),
+                                            out.ctypes.data, len(out)), "cse_stoi_layout")
+        return dict(zip(_lib.STOI_LAYOUT_FIELDS, (int(v) for v in out)))
+
+    def stages(self):
+        """The clean side's stages as typed views of self.ws (no copy), for
+        tests and tools: coef [5, 128] (16 kHz) or None, meta [S, META] (K, M,
+        J, ok, nblk), x10 [S, n10], en [S, F], kf [S, F], btab [S, NBLK, BT],
+        xtob [S, Mmax, 16], xstat [S, Jmax, 16, 4], hgen [taps] (other rates)
+        or None, xcol [S, Jmax, 30, 2] (extended) or None, and "layout".
+        Rows >= M, column 15 and entries past K / nblk are unspecified."""
+        lay = self.layout()
+        S = self.S
+
+        def view(name, dtype, shape):
+            n = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+            return self.ws[lay[name]:lay[name] + n].view(dtype).view(*shape)
+
+        f64, i32 = torch.float64, torch.int32
+        out = {
+            "layout": lay,
+            "coef": view("coef64", f64, (5, 128)) if self.sr == STOI_SR else None,
+            "meta": view("meta", i32, (S, lay["META"])),
+            "x10": view("x10", f64, (S, lay["n10"])),
+            "en": view("en", f64, (S, lay["F"])),
+            "kf": view("kf", i32, (S, lay["F"])),
+            "btab": view("btab", i32, (S, lay["NBLK"], lay["BT"])),
+            "xtob": view("xtob", f64, (S, lay["Mmax"], 16)),
+            "xstat": view("xstat", f64, (S, lay["Jmax"], 16, 4)),
+            "hgen": None if self.sr == STOI_SR else view("hgen", f64, (lay["ntap"],)),
+            "xcol": view("xcol", f64, (S, lay["Jmax"], 30, 2)) if self.extended else None,
+        }
+        return out
+
+    def cell_envelopes(self, n):
+        """Band envelopes [n, Mmax, 16] of the n <= STOI_CHUNK cells the last
+        score / score_async scored (a view of the scratch; rows >= M of the
+        cell's signal and column 15 are unspecified)."""
+        if not 0 < n <= STOI_CHUNK or self._scratch is None:
+            raise ValueError("cell_envelopes: after a score of 1..STOI_CHUNK cells")
+        Mmax = self.layout()["Mmax"]
+        return self._scratch[:n * Mmax * 128].view(torch.float64).view(n, Mmax, 16)
+
+    def cell_y10(self, n):
+        """At rates other than 16 kHz: the 10-kHz test signals [n, n10] of the
+        n <= STOI_CHUNK cells the last score scored (the scratch after the
+        envelopes)."""
+        if self.sr == STOI_SR:
+            raise ValueError("cell_y10: 16-kHz cells are resampled inside the cell kernel")
+        if not 0 < n <= STOI_CHUNK or self._scratch is None:
+            raise ValueError("cell_y10: after a score of 1..STOI_CHUNK cells")
+        lay = self.layout()
+        o = n * lay["Mmax"] * 128
+        return self._scratch[o:o + n * lay["n10"] * 8].view(torch.float64).view(n, lay["n10"])
+
 
 SEGSNR_RATES = (16000, 8000)
 # bound on the scratch of one cse_segsnr_cells launch: the cells per launch come

@@ -96,6 +96,33 @@ def test_stoi_rates(lib):
                                0, 1, n, 900000, 1, ctypes.c_void_p(16), None, ctypes.c_void_p(16),
                                None)
     assert rc == -1 and b"sr=900000" in lib.cse_last_error()
+    # cse_stoi_layout (include/cse_stoi_stages.h: a header of its own, cse.h's
+    # code being part of the enhance kernels' pinned source digest) refuses
+    # what the size functions refuse, and a short out
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(os.path.dirname(HEADER),
+                                                      "cse_stoi_stages.h")).read(), flags=re.S)
+    assert set(re.findall(r"\b(cse_[a-z0-9_]+)\s*\(", text)) == set(_lib.EXPORTS_STOI_STAGES)
+    assert not set(_lib.EXPORTS_STOI_STAGES) & set(_lib.EXPORTS)
+    assert f"#define CSE_STOI_LAYOUT_N {len(_lib.STOI_LAYOUT_FIELDS)}\n" in text
+    assert lib.cse_version() == _lib.ABI_VERSION == 5  # an addition: the revision stays
+    out = np.zeros(len(_lib.STOI_LAYOUT_FIELDS), dtype=np.int64)
+    for sr in (999, 768001, -16000):
+        assert lib.cse_stoi_layout(1, n, sr, 0, out.ctypes.data, len(out)) == -1
+        assert f"cse_stoi_layout: sr={sr}".encode() in lib.cse_last_error()
+    for n_sig, length in ((0, n), (1, 0)):
+        assert lib.cse_stoi_layout(n_sig, length, 16000, 0, out.ctypes.data, len(out)) == -1
+        assert b"cse_stoi_layout: n_sig=" in lib.cse_last_error()
+    assert lib.cse_stoi_layout(1, n, 16000, 0, out.ctypes.data, len(out) - 1) == -1
+    assert b"cse_stoi_layout: n_out=20" in lib.cse_last_error()
+    assert lib.cse_stoi_layout(1, n, 16000, 0, None, len(out)) == -1
+    assert b"cse_stoi_layout: NULL out" in lib.cse_last_error()
+    for sr in (16000, 8000, 10000, 22050, 44100, 48000):
+        for ext, size in ((0, lib.cse_stoi_workspace_bytes_sr), (1, lib.cse_estoi_workspace_bytes)):
+            assert lib.cse_stoi_layout(2, n, sr, ext, out.ctypes.data, len(out)) == 0
+            L = dict(zip(_lib.STOI_LAYOUT_FIELDS, out.tolist()))
+            assert L["total"] == size(2, n, sr)
+            assert (L["xcol"] >= L["hgen"]) if ext else (L["xcol"] == -1)
+            assert L["n10"] == -(-n * 10000 // sr)
 
 
 def test_route_classes_pack_in_order():
